@@ -9,8 +9,11 @@ verification -> post-refinement) over --pairs synthetic scan pairs of
 collective (weak scaling); the only collectives are the barrier around the
 timed region and a max-reduce of the elapsed time.
 
-Prints ONE JSON line (rank 0).  Also measured live with HIP events on the
-stream the kernels run on:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps
+forwards and prints the headline (value, ms_per_step); --dump-outputs DIR also
+writes the last timed step's results (final_trans, final_labels) as DIR/<name>.npy.
+Everything below runs only with --full, after the timed steps, and adds its keys
+to the same line.  Measured live with HIP events on the stream the kernels run on:
   roofline      -- the dominant kernel (SCNonlocal attention), MFMA bound; its fp32
                    products run as 3 fp16 MFMAs, so the peak is 2500/3 TFLOP/s
   roofline_hbm  -- the forward's a1 compatibility kernel (symmetric-packed M), HBM-write bound;
@@ -62,6 +65,11 @@ def parse():
     ap.add_argument("--num-corr", type=int, default=1000)
     ap.add_argument("--pairs", type=int, default=128, help="scan pairs per GPU per step")
     ap.add_argument("--preset", default="3dmatch", choices=["3dmatch", "kitti"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the rooflines, per-stage times, single-pair, ragged and "
+                         "exact-fp32 legs, the recall gather and the CPU baseline / parity (the options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-iters", type=int, default=20, help="launches per standalone-kernel timing (>= 1)")
@@ -181,6 +189,22 @@ def event_time(fn, iters, stream):
         end.record(stream)
     end.synchronize()
     return start.elapsed_time(end) / iters
+
+
+DUMP_MAX_BYTES = 64 << 20  # of one run's dump, all arrays and ranks together
+
+
+def dump_outputs(path, arrays, rank, world):
+    """--dump-outputs: this rank's arrays (what a caller of the timed path receives)
+    as float32 .npy files.  An array past its share of DUMP_MAX_BYTES is written as a
+    fixed sample instead: the flat elements at seeded (RandomState(0)), sorted indices."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // (4 * world * len(arrays))  # float32 elements per array
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 def free_port():
@@ -316,49 +340,80 @@ def main():
         if grp:
             torch.distributed.barrier()
 
-    # HIP events around every attention launch inside the timed region (the
+    # --full: HIP events around every attention launch inside the timed region (the
     # dominant kernel), recorded on the stream the kernels run on
     import ctypes
     L = _lib.load()
     # (on the LAST timed step only: a timed event pair around every launch of every
     # step costs the step ~1 %, and 70 us per single-pair forward -- measured r04)
-    evs = HipEvents(12)
+    evs = HipEvents(12) if args.full else None
     barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if i == args.steps - 1:
+        if evs is not None and i == args.steps - 1:
             _lib.check(L.pdsc_attention_timing(evs.start, evs.stop, evs.n, ctypes.byref(evs.count)),
                        "pdsc_attention_timing")
         plan.run(corr, src, tgt)
     torch.cuda.synchronize(dev)
     barrier()
     elapsed = time.perf_counter() - t0
-    L.pdsc_attention_timing(None, None, 0, None)
-    att_times = [evs.elapsed_ms(i) for i in range(evs.count.value)]
-    # per-stage ms from 3 more forwards with the stage events (outside the clock: a
-    # stage-timed forward runs a1 on the caller's stream, not beside the encoder)
-    sev = EventPool(3 * (len(STAGES) + 1))
-    _lib.check(L.pdsc_forward_timing(sev.ev, sev.n, ctypes.byref(sev.count)), "pdsc_forward_timing")
-    for _ in range(3):
-        plan.run(corr, src, tgt)
-    torch.cuda.synchronize(dev)
-    L.pdsc_forward_timing(None, 0, None)
+    if evs is not None:
+        L.pdsc_attention_timing(None, None, 0, None)
+        att_times = [evs.elapsed_ms(i) for i in range(evs.count.value)]
+    # the last timed step's results, before any later forward writes the plan's buffers again
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"final_trans": plan.trans, "final_labels": plan.labels}, rank, world)
+    # the fp16 range guard's marks of the last timed step (include/pdsc.h; after the clock)
+    range_marked = len(plan.range_flags())
+    if range_marked:
+        log(f"[rank {rank}] WARNING: {range_marked} pairs marked by the fp16 range guard")
+    if args.full:
+        # per-stage ms from 3 more forwards with the stage events (outside the clock: a
+        # stage-timed forward runs a1 on the caller's stream, not beside the encoder)
+        sev = EventPool(3 * (len(STAGES) + 1))
+        _lib.check(L.pdsc_forward_timing(sev.ev, sev.n, ctypes.byref(sev.count)), "pdsc_forward_timing")
+        for _ in range(3):
+            plan.run(corr, src, tgt)
+        torch.cuda.synchronize(dev)
+        L.pdsc_forward_timing(None, 0, None)
     own_elapsed = elapsed
     elapsed_min = elapsed
     if grp:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        tmin = torch.tensor([own_elapsed], device=dev, dtype=torch.float64)
-        torch.distributed.all_reduce(tmin, op=torch.distributed.ReduceOp.MIN)
-        elapsed, elapsed_min = float(t.item()), float(tmin.item())
+        elapsed = float(t.item())
+        if args.full:
+            tmin = torch.tensor([own_elapsed], device=dev, dtype=torch.float64)
+            torch.distributed.all_reduce(tmin, op=torch.distributed.ReduceOp.MIN)
+            elapsed_min = float(tmin.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = world * P * N * args.steps / elapsed
-    # the fp16 range guard's marks of the last timed step (include/pdsc.h; after the clock)
-    range_marked = len(plan.range_flags())
-    if range_marked:
-        log(f"[rank {rank}] WARNING: {range_marked} pairs marked by the fp16 range guard")
     log(f"[rank {rank}] {ms_per_step:.3f} ms/step -> {value:.4g} correspondences/s")
+
+    headline = {
+        "metric": "correspondence-pairs/sec through NSM (N=1k/5k) at 1/2/4/8 GPUs; 3DMatch recall parity",
+        "value": round(value, 1), "unit": "correspondences/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32 (3xf16-split contractions)",
+        "dtype_note": "fp32 inputs, outputs and accumulation; the attention, 1x1-conv and kNN/NSM "
+                      "contractions run as 3 fp16 MFMA products (hi*hi + hi*lo + lo*hi) per fp32 product",
+        "data": "synthetic",
+        "config": {"workload": f"synthetic random correspondences N={N} ({args.preset}-like, 30% inliers), "
+                               f"{P} scan pairs per GPU per step, full PointDSC testing forward "
+                               f"(12 layers x 128 ch, trained synthetic weights, classifier rescaled "
+                               f"by synthetic.BENCH_CLS for tie-free seed ranking)",
+                   "num_corr": N, "pairs_per_gpu_per_step": P, "global_batch": P * world,
+                   "parallelism": f"dp{world} (independent pairs)"},
+        "scan_pairs_per_s": round(world * P * args.steps / elapsed, 2),
+        "range_marked_pairs": range_marked,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if grp:
+            torch.distributed.destroy_process_group()
+        return
 
     # the last step's per-pair result rows (libs/loss.py metrics, evaluate.pair_stats), gathered
     # over all ranks with one all_gather (RCCL over xGMI for W > 1): registration recall of the job
@@ -666,20 +721,7 @@ def main():
                            "travel to the GPU box"}
 
         result = {
-            "metric": "correspondence-pairs/sec through NSM (N=1k/5k) at 1/2/4/8 GPUs; 3DMatch recall parity",
-            "value": round(value, 1), "unit": "correspondences/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32 (3xf16-split contractions)",
-            "dtype_note": "fp32 inputs, outputs and accumulation; the attention, 1x1-conv and kNN/NSM "
-                          "contractions run as 3 fp16 MFMA products (hi*hi + hi*lo + lo*hi) per fp32 product",
-            "data": "synthetic",
-            "config": {"workload": f"synthetic random correspondences N={N} ({args.preset}-like, 30% inliers), "
-                                   f"{P} scan pairs per GPU per step, full PointDSC testing forward "
-                                   f"(12 layers x 128 ch, trained synthetic weights, classifier rescaled "
-                                   f"by synthetic.BENCH_CLS for tie-free seed ranking)",
-                       "num_corr": N, "pairs_per_gpu_per_step": P, "global_batch": P * world,
-                       "parallelism": f"dp{world} (independent pairs)"},
-            "scan_pairs_per_s": round(world * P * args.steps / elapsed, 2),
+            **headline,
             "synthetic_recall": recall, "pairs_gathered": int(allrows.shape[0]),
             # self-check of the multi-rank run (the driver's SCALE runs): the process group's size,
             # the spread of the ranks' own timed regions, and every global pair gathered once
@@ -689,7 +731,6 @@ def main():
                                                  "max": round(ms_per_step, 4)},
                             "pairs_expected": P * world, "pairs_gathered": int(allrows.shape[0]),
                             "pair_ids_ok": pair_ids_ok},
-            "range_marked_pairs": range_marked,
             "roofline": roofline, "roofline_hbm": roofline_hbm, "roofline_hbm_dense": roofline_hbm_dense,
             "roofline_path": roofline_path,
             "roofline_sm": roofline_sm,

@@ -32,7 +32,7 @@ def _torchrun(args, timeout=300):
 @pytest.mark.gpu
 def test_bench_one_rank_rccl():
     out = _torchrun(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "16",
-                     "--no-cpu-baseline", "--f32-steps", "0", "--path-n", "0"])
+                     "--full", "--no-cpu-baseline", "--f32-steps", "0", "--path-n", "0"])
     assert len(out) == 1
     res = out[0]
     assert res["n_gpus"] == 1 and res["pairs_gathered"] == 16 and res["value"] > 0

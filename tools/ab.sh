@@ -11,7 +11,7 @@ for r in $(seq 1 "$rounds"); do
     lv=$v; knob=PDSC_AB_NONE=1; [ "$v" = "-" ] && lv=""
     case "$v" in *=*) knob=$v; lv="";; esac
     out=gpurun_out/${name}_${v}_$r.log
-    env "$knob" PDSC_LIB_VARIANT=$lv timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --f32-steps 0 \
+    env "$knob" PDSC_LIB_VARIANT=$lv timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --f32-steps 0 \
         --path-n ${PATH_N:-0} ${BENCH_ARGS} > "$out" 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "variant $v rc=$rc"; tail -5 "$out"; exit $rc; fi

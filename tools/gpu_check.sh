@@ -12,4 +12,4 @@ step() {  # name timeout cmd...
 }
 step pytest_gpu 900 python -m pytest tests -q -m gpu --timeout 120 --timeout-method thread -p no:cacheprovider ${PYTEST_ARGS}
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py --steps 5 --warmup 2
+step bench 600 python bench.py --full --steps 5 --warmup 2

@@ -9,7 +9,7 @@ OUT="$R/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-BENCH=(python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline "$@")
+BENCH=(python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline "$@")
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- "${BENCH[@]}" \
     > "$OUT/trace.log" 2>&1 || { echo "trace rc=$?"; tail -20 "$OUT/trace.log"; exit 1; }
 echo "trace ok"
