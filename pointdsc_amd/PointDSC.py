@@ -383,7 +383,10 @@ class PointDSC(nn.Module):
         call (pdsc_forward_testing_ragged).  Each element is a ``forward`` input
         dict (tensors [1,n,.] or [n,.]; the 'testing' key is implied); returns one
         ``forward`` result dict per element: final_trans [1,4,4], final_labels
-        [1,n], M None -- equal to calling ``forward`` on each."""
+        [1,n], M None.  Against calling ``forward`` on each: labels bitwise equal;
+        poses within 1e-4, or a seed / kNN near-tie apart (another launch plan
+        sums in another fp32 order, which can decide a near-tie the other way;
+        DESIGN.md §5) -- poses are not bitwise equal across launch plans."""
         if not datas:
             return []
         corr, counts = kernels.pad_pairs([d["corr_pos"] for d in datas])

@@ -6,10 +6,13 @@ replaces (knob PDSC_ATT_WS=1), run with -m gpu.
 Both compute each query's softmax over the same keys; only the fp32 order in
 which a split's tiles are summed differs (per-wave runs merged by 2^(m_w - m*)).
 Per shape: the forward's logits agree within 1e-4 x (1 + max |logit|), no NaN,
-labels equal, and poses within 1e-4 -- or, where the two summation orders
+and the labels of the two kernels are equal -- required of every pair, before
+any fallback runs.  Poses within 1e-4 -- or, where the two summation orders
 decided a seed / kNN near-tie differently, BOTH results held to the oracle by
-the near-tie rule (conftest.assert_held_to_oracle), as the other cross-plan
-tests do."""
+the near-tie rule (tests/parity_rules.py: logits within the pair's fp32
+envelope, seeds and kNN rows different only by near-ties, the oracle on our
+seeds and kNN rows within 1e-4), as the other cross-plan tests do.  The test
+prints how many of its 5 pairs took that fallback and caps the count."""
 import os
 import subprocess
 import sys
@@ -18,7 +21,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import assert_held_to_oracle
+from parity_rules import NearTieTally, held_to_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -59,7 +62,7 @@ def _dump(path):
     np.savez(path, **out)
 
 
-def test_wave_split_matches_one_wave(gpu_device, tmp_path):
+def test_wave_split_matches_one_wave(gpu_device, tmp_path, capsys):
     here = os.path.dirname(os.path.abspath(__file__))
     res = {}
     for knob in ("1", "4"):
@@ -69,6 +72,7 @@ def test_wave_split_matches_one_wave(gpu_device, tmp_path):
         subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PDSC_ATT_WS=knob), check=True, timeout=300)
         res[knob] = np.load(path)
     _, sd = _model_sd()
+    tally = NearTieTally("test_wave_split_matches_one_wave")
     for i, (B, N) in enumerate(CASES):
         a, b = res["1"][f"conf{i}"], res["4"][f"conf{i}"]
         assert np.isfinite(a).all() and np.isfinite(b).all(), (B, N)
@@ -79,11 +83,14 @@ def test_wave_split_matches_one_wave(gpu_device, tmp_path):
             what = f"B={B} N={N} pair {p}"
             assert np.array_equal(res["1"][f"final_labels{i}"][p], res["4"][f"final_labels{i}"][p]), what
             dT = float(np.abs(res["1"][f"final_trans{i}"][p] - res["4"][f"final_trans{i}"][p]).max())
+            tally.add(dT, fallback=not dT <= 1e-4)
             if dT <= 1e-4:
                 continue
             q = {k: d[k][p] for k in ("corr_pos", "src_keypts", "tgt_keypts")}
             for knob in ("1", "4"):
                 r = res[knob]
-                assert_held_to_oracle(q, r[f"final_labels{i}"][p], r[f"final_trans{i}"][p], r[f"conf{i}"][p],
-                                      r[f"seeds{i}"][p], r[f"knn{i}"][p], sd, f"{what} WS={knob} (dT {dT:.3g})",
-                                      num_layers=12)
+                held_to_oracle(q, r[f"final_labels{i}"][p], r[f"final_trans{i}"][p], r[f"conf{i}"][p],
+                               r[f"seeds{i}"][p], r[f"knn{i}"][p], sd, gpu_device, f"{what} WS={knob} (dT {dT:.3g})",
+                               tally=tally, count=False, num_layers=12)
+    assert tally.pairs == sum(B for B, _ in CASES)
+    tally.finish(capsys)

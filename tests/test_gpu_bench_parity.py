@@ -36,6 +36,7 @@ import torch
 
 from conftest import (ENVELOPE, LOGIT_FLOOR, assert_knn_equivalent, assert_seeds_near_ties, fp32_envelope,
                       load_golden)
+from parity_rules import NearTieTally
 
 pytestmark = pytest.mark.gpu
 
@@ -146,7 +147,9 @@ def test_b65_both_attention_plans_vs_reference(gpu_device, capsys):
     rules above: labels bit-exact on all 65 pairs, poses within 1e-4 or the
     near-tie explanation (logits within the fp32 envelope, seeds / kNN rows
     different only by near-ties, the oracle on our seeds and kNN rows within
-    1e-4).  The distances of both plans are printed for the record."""
+    1e-4).  The distances of both plans are printed for the record, and each
+    plan's count of pairs that took the explanation (parity_rules.NearTieTally:
+    65 pairs, at most 5)."""
     import ctypes
     from pointdsc_amd import _lib, kernels
     from pointdsc_amd.PointDSC import PointDSC
@@ -179,8 +182,13 @@ def test_b65_both_attention_plans_vs_reference(gpu_device, capsys):
         assert np.array_equal(st["final_labels"].astype(np.uint8), g["final_labels"][:P]), name
         d = np.abs(st["final_trans"] - g["final_trans"][:P]).reshape(P, -1).max(1)
         far = np.nonzero(d > POSE_ATOL)[0]
+        tally = NearTieTally(f"test_b65_both_attention_plans_vs_reference, {name}")
+        for i in range(P):
+            tally.add(d[i], fallback=not d[i] <= POSE_ATOL)
         for i in far:
             _explain(int(i), g, st, ps, sd, p, gpu_device)
+        tally.finish(capsys)
+        assert tally.pairs == 65 and tally.cap == 5
         report[name] = {"max_pose_diff": float(d.max()), "pairs_past_1e-4": far.tolist()}
     dd = float((uni["final_trans"] - T2).abs().max())
     with capsys.disabled():
