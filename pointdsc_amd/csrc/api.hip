@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "attention_plan.hpp"
 #include "pdsc_internal.hpp"
 
 using namespace pdsc;
@@ -63,20 +64,6 @@ struct Carve {
     }
 };
 
-// A/B knob (measurement only): PDSC_DENSE_M=1 makes the forward write and read M dense.
-bool dense_m_requested() {
-    static const bool v = [] {
-        const char *e = getenv("PDSC_DENSE_M");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
-
-// The forward's M layout: symmetric-packed for the H3 plans, dense for exact fp32
-// (and PDSC_DENSE_M=1 on the h3 plans other than attention_w64's, measurement only).
-struct Dims;
-int forward_m_layout(const Dims &d);
-
 int check_cfg(const pdsc_config *cfg) {
     if (!cfg) return fail(PDSC_ERR_ARG, "cfg is NULL");
     if (cfg->num_channels != CH)
@@ -92,28 +79,14 @@ int check_cfg(const pdsc_config *cfg) {
     return PDSC_OK;
 }
 
-// The tiniest batches (<= 16 query blocks of 128, >= 16 key splits: a single
-// N = 1000 pair) combine the attention partials in their own launch
-// (combine_rows) rather than in the pointwise kernel's prologue: measured
-// 0.511 -> 0.482 ms per single-pair forward, but slower from 4 pairs of
-// N = 1000 on (an extra launch per layer).  A/B knob PDSC_PRECOMBINE=0 (never).
-static bool use_precombine(int B, int Npad, int nsplit, bool f32, bool fuse) {
-    static const bool off = [] {
-        const char *e = getenv("PDSC_PRECOMBINE");
-        return e && e[0] == '0';
-    }();
-    return !off && !f32 && !fuse && nsplit >= 16 && (long)B * (Npad / QB) <= 16;
-}
-
 struct Dims {
-    int B, N, Npad, S, k, T, nsplit;
-    bool f32;   // PDSC_PRECISION_F32
-    bool fuse;  // attention + pointwise chain in one launch per layer (attention_fused)
-    bool w64;   // split path with attention_w64 (64-query waves)
-    bool precombine;  // split partials combined by combine_rows ahead of the pointwise kernels
+    int B, N, Npad, S, k, T;
+    bool f32;          // PDSC_PRECISION_F32
+    EncoderPlan plan;  // the encoder's attention plan for (B, N, f32)
 };
 
-int make_dims(const pdsc_config *cfg, int B, int N, Dims &d) {
+// dense_m_caller: the standalone encoder's plan, on the caller's dense M (plan_encoder)
+int make_dims(const pdsc_config *cfg, int B, int N, Dims &d, bool dense_m_caller = false) {
     if (B < 1 || N < 2) return fail(PDSC_ERR_ARG, "B=%d N=%d (need B >= 1, N >= 2)", B, N);
     if (N > 32767) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > 32767 (32-bit buffer descriptors over M)", N);
     d.B = B;
@@ -123,18 +96,10 @@ int make_dims(const pdsc_config *cfg, int B, int N, Dims &d) {
     d.k = std::min(cfg->k, N - 1);        // (:250)
     d.T = cfg->num_iterations;
     d.f32 = cfg->precision == PDSC_PRECISION_F32;
-    d.fuse = attention_fused(B, N, d.f32);
-    d.w64 = !d.fuse && attention_w64(B, N, d.f32);
-    d.nsplit = attention_nsplit(B, N, d.f32, d.w64);
-    d.precombine = use_precombine(B, d.Npad, d.nsplit, d.f32, d.fuse);
+    d.plan = plan_encoder(B, N, d.f32, dense_m_caller);
     if (d.S < 1) return fail(PDSC_ERR_ARG, "int(N*ratio) = 0 seeds for N=%d", N);
     if (d.k > 63) return fail(PDSC_ERR_UNSUPPORTED, "k=%d > 63", d.k);
     return PDSC_OK;
-}
-
-int forward_m_layout(const Dims &d) {
-    if (d.w64) return M_PACKED;
-    return (!dense_m_requested() && !d.f32) ? M_PACKED : M_DENSE;
 }
 
 struct EncBufs {
@@ -142,7 +107,7 @@ struct EncBufs {
     float *feat2;            // the split path's second feat buffer (pw_mid reads one, writes the other), else null
     _Float16 *q, *k, *v;     // attention_h3 split layouts (hi + lo per element), or fp32 rows (F32)
     _Float16 *q2, *k2, *v2;  // the other Q/K/V set of the fused path (layers alternate), else null
-    float *opart1, *ml1;     // the combined split (Dims::precombine), else null
+    float *opart1, *ml1;     // the combined split (EncoderPlan::precombine), else null
 };
 
 EncBufs carve_encoder(Carve &c, const Dims &d) {
@@ -152,19 +117,19 @@ EncBufs carve_encoder(Carve &c, const Dims &d) {
     e.q = c.take<_Float16>(2 * rows);
     e.k = c.take<_Float16>(2 * rows);
     e.v = c.take<_Float16>(2 * rows);
-    e.opart = c.take<float>(rows * d.nsplit);
-    e.ml = c.take<float>((size_t)d.B * d.Npad * d.nsplit * 2);
+    e.opart = c.take<float>(rows * d.plan.nsplit);
+    e.ml = c.take<float>((size_t)d.B * d.Npad * d.plan.nsplit * 2);
     e.vexp = c.take<float>((size_t)d.B * (d.Npad / 32));
-    e.opart1 = d.precombine ? c.take<float>(rows) : nullptr;
-    e.ml1 = d.precombine ? c.take<float>((size_t)d.B * d.Npad * 2) : nullptr;
+    e.opart1 = d.plan.precombine ? c.take<float>(rows) : nullptr;
+    e.ml1 = d.plan.precombine ? c.take<float>((size_t)d.B * d.Npad * 2) : nullptr;
     e.q2 = e.k2 = e.v2 = nullptr;
     e.vexp2 = nullptr;
     // pw_mid's three Q / K / V workgroups per point tile all read the layer's
     // residual rows while one of them writes the new PointCN rows: the rows
     // ping-pong between feat and feat2 so no workgroup overwrites what another
     // still reads
-    e.feat2 = d.fuse ? nullptr : c.take<float>(rows);
-    if (d.fuse) {
+    e.feat2 = d.plan.fused() ? nullptr : c.take<float>(rows);
+    if (d.plan.fused()) {
         e.q2 = c.take<_Float16>(2 * rows);
         e.k2 = c.take<_Float16>(2 * rows);
         e.v2 = c.take<_Float16>(2 * rows);
@@ -173,43 +138,39 @@ EncBufs carve_encoder(Carve &c, const Dims &d) {
     return e;
 }
 
-int run_encoder(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M,
-                int m_layout, const Dims &d, const EncBufs &e, float *feat_out, float *normed,
-                _Float16 *normed_s, float *conf, hipStream_t s, Ragged rg = {}) {
-    const bool m_packed = m_layout == M_PACKED;
-    const bool w64 = d.w64 && !d.fuse;
-    if (w64 && m_layout != M_PACKED) return fail(PDSC_ERR_ARG, "M layout %d for this plan", m_layout);
+// M: in the plan's layout (d.plan.m_layout)
+int run_encoder(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M, const Dims &d,
+                const EncBufs &e, float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
+                Ragged rg = {}) {
+    const EncoderPlan plan = d.plan.for_ragged(rg);
     HIPCHK(launch_pw_first(packed, lay, corr_pos, d.f32, d.B, d.N, d.Npad, e.feat, e.q, e.k, e.v, e.vexp, s, rg,
-                           d.fuse));
-    if (d.fuse) {  // every layer fused (0 .. L-2 with the next layer's PointCN/QKV, Q/K/V alternating between the two sets)
+                           plan.fused()));
+    if (plan.fused()) {  // every layer fused (0 .. L-2 with the next layer's PointCN/QKV, Q/K/V alternating between the two sets)
         _Float16 *q = e.q, *k = e.k, *v = e.v, *q2 = e.q2, *k2 = e.k2, *v2 = e.v2;
         float *vx = e.vexp, *vx2 = e.vexp2;
         for (int l = 0; l + 1 < lay.L; ++l) {
             const bool timed = g_tcap > 0 && g_tcount && *g_tcount < g_tcap;
             if (timed) HIPCHK(hipEventRecord(g_tstart[*g_tcount], s));
-            HIPCHK(launch_attn_pw2(packed, lay, l, q, k, v, vx, M, m_packed, d.B, d.N, d.Npad, e.feat, q2, k2, v2, vx2,
-                                   s, rg));
+            HIPCHK(launch_attn_pw2(plan, packed, lay, l, q, k, v, vx, M, e.feat, q2, k2, v2, vx2, s, rg));
             if (timed) HIPCHK(hipEventRecord(g_tstop[(*g_tcount)++], s));
             std::swap(q, q2);
             std::swap(k, k2);
             std::swap(v, v2);
             std::swap(vx, vx2);
         }
-        HIPCHK(launch_attn_pw2_last(packed, lay, q, k, v, vx, M, m_packed, d.B, d.N, d.Npad, e.feat, feat_out, normed,
-                                    normed_s, conf, s, rg));
+        HIPCHK(launch_attn_pw2_last(plan, packed, lay, q, k, v, vx, M, e.feat, feat_out, normed, normed_s, conf, s, rg));
         return PDSC_OK;
     }
     float *feat = e.feat, *feat_alt = e.feat2;
     for (int l = 0; l < lay.L; ++l) {
         const bool timed = g_tcap > 0 && g_tcount && *g_tcount < g_tcap;
         if (timed) HIPCHK(hipEventRecord(g_tstart[*g_tcount], s));
-        HIPCHK(launch_attention(e.q, e.k, e.v, e.vexp, M, m_layout, w64, d.f32, d.B, d.N, d.Npad, d.nsplit, e.opart,
-                                e.ml, s, rg, l));
+        HIPCHK(launch_attention(plan, e.q, e.k, e.v, e.vexp, M, e.opart, e.ml, s, rg, l));
         if (timed) HIPCHK(hipEventRecord(g_tstop[(*g_tcount)++], s));
         const float *op = e.opart, *mlp = e.ml;
-        int ns = d.nsplit;
-        if (d.precombine) {
-            HIPCHK(launch_combine_rows(e.opart, e.ml, d.B, d.Npad, d.nsplit, e.opart1, e.ml1, s));
+        int ns = plan.nsplit;
+        if (plan.precombine) {
+            HIPCHK(launch_combine_rows(e.opart, e.ml, d.B, d.Npad, plan.nsplit, e.opart1, e.ml1, s));
             op = e.opart1;
             mlp = e.ml1;
             ns = 1;
@@ -267,7 +228,7 @@ static bool enc_work_balanced() {
 }
 static bool enc_halves(const Dims &d, bool ragged) {
     const int mode = enc_halves_mode();
-    return d.fuse && d.B >= 16 * enc_parts() && (mode == 2 || (mode == 1 && ragged));
+    return d.plan.fused() && d.B >= 16 * enc_parts() && (mode == 2 || (mode == 1 && ragged));
 }
 // Part boundaries bounds[0 .. P]: bounds[i] = the first pair whose work prefix
 // reaches i/P of the total (counts: HOST sizes, or NULL for a uniform batch).
@@ -318,10 +279,11 @@ static SideStream *side_stream(hipStream_t s) {
 // The fused plan's encoder over pairs [b0, b0 + nb): every per-pair pointer
 // moved to pair b0 (the pair-major layouts of carve_encoder / carve_forward).
 static int run_encoder_part(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M,
-                            int m_layout, const Dims &d, const EncBufs &e, float *normed, _Float16 *normed_s,
-                            float *conf, hipStream_t s, Ragged rg, int b0, int nb) {
+                            const Dims &d, const EncBufs &e, float *normed, _Float16 *normed_s, float *conf,
+                            hipStream_t s, Ragged rg, int b0, int nb) {
     Dims dh = d;
     dh.B = nb;
+    dh.plan = d.plan.for_pairs(nb);  // the batch's plan, not nb pairs' own
     const size_t rows = (size_t)b0 * d.Npad * CH;
     EncBufs eh = e;
     eh.feat = e.feat + rows;
@@ -333,14 +295,14 @@ static int run_encoder_part(const PackLayout &lay, const float *packed, const fl
     eh.v2 = e.v2 + 2 * rows;
     eh.vexp = e.vexp + (size_t)b0 * (d.Npad / 32);
     eh.vexp2 = e.vexp2 + (size_t)b0 * (d.Npad / 32);
-    const size_t mstr = m_layout == M_PACKED ? mpack_floats(d.N) : (size_t)d.N * d.N;
+    const size_t mstr = d.plan.m_layout == M_PACKED ? mpack_floats(d.N) : (size_t)d.N * d.N;
     Ragged rh = rg;
     if (rg.nv) rh.nv = rg.nv + b0;
     if (rg.sv) rh.sv = rg.sv + b0;
     if (rg.po) rh.po = rg.po + b0;
-    return run_encoder(lay, packed, corr_pos + (size_t)b0 * d.N * lay.in_dim, M + (size_t)b0 * mstr, m_layout, dh,
-                       eh, nullptr, normed + (size_t)b0 * d.N * CH, normed_s + (size_t)b0 * d.N * 2 * CH,
-                       conf + (size_t)b0 * d.N, s, rh);
+    return run_encoder(lay, packed, corr_pos + (size_t)b0 * d.N * lay.in_dim, M + (size_t)b0 * mstr, dh, eh, nullptr,
+                       normed + (size_t)b0 * d.N * CH, normed_s + (size_t)b0 * d.N * 2 * CH, conf + (size_t)b0 * d.N, s,
+                       rh);
 }
 
 // run_encoder for the forward: the fused plan as P concurrent parts given side
@@ -348,9 +310,9 @@ static int run_encoder_part(const PackLayout &lay, const float *packed, const fl
 // must then order each part's pairs on its own: launch_ragged_order per part),
 // else run_encoder itself.
 static int run_encoder_fwd(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M,
-                           int m_layout, const Dims &d, const EncBufs &e, float *normed, _Float16 *normed_s,
-                           float *conf, hipStream_t s, Ragged rg, SideStream *ss, const int *bounds, int P) {
-    if (!ss) return run_encoder(lay, packed, corr_pos, M, m_layout, d, e, nullptr, normed, normed_s, conf, s, rg);
+                           const Dims &d, const EncBufs &e, float *normed, _Float16 *normed_s, float *conf,
+                           hipStream_t s, Ragged rg, SideStream *ss, const int *bounds, int P) {
+    if (!ss) return run_encoder(lay, packed, corr_pos, M, d, e, nullptr, normed, normed_s, conf, s, rg);
     std::lock_guard<std::mutex> lock(ss->mu);
     // The side streams are shared by every caller stream of the device.  A side
     // stream forked into another thread's graph capture stays in that capture
@@ -364,7 +326,7 @@ static int run_encoder_fwd(const PackLayout &lay, const float *packed, const flo
         for (int i = 1; i < P; ++i) {
             HIPCHK(hipStreamGetCaptureInfo(ss->s2[i - 1], &c2, &id2));
             if (c2 != hipStreamCaptureStatusNone && (cs != hipStreamCaptureStatusActive || id2 != id))
-                return run_encoder(lay, packed, corr_pos, M, m_layout, d, e, nullptr, normed, normed_s, conf, s, rg);
+                return run_encoder(lay, packed, corr_pos, M, d, e, nullptr, normed, normed_s, conf, s, rg);
         }
     }
     HIPCHK(hipEventRecord(ss->fork, s));
@@ -375,8 +337,8 @@ static int run_encoder_fwd(const PackLayout &lay, const float *packed, const flo
             break;
         }
     for (int i = 0; r == PDSC_OK && i < P; ++i)
-        r = run_encoder_part(lay, packed, corr_pos, M, m_layout, d, e, normed, normed_s, conf,
-                             i ? ss->s2[i - 1] : s, rg, bounds[i], bounds[i + 1] - bounds[i]);
+        r = run_encoder_part(lay, packed, corr_pos, M, d, e, normed, normed_s, conf, i ? ss->s2[i - 1] : s, rg,
+                             bounds[i], bounds[i + 1] - bounds[i]);
     // join every side stream that was forked, on success AND on error: the
     // caller's stream must not run ahead of work a side stream may still do in
     // the workspace, and a capture must not end with an unjoined fork
@@ -605,17 +567,10 @@ int32_t pdsc_compat_packed_f32(const float *src, const float *tgt, int32_t B, in
 }
 
 // ---------------------------------------------------------------- a2-a4
-// the standalone encoder takes the caller's dense M: its plan never runs attention_w64
-static void dims_dense_m(Dims &d) {
-    d.w64 = false;
-    d.nsplit = attention_nsplit(d.B, d.N, d.f32, false);
-    d.precombine = use_precombine(d.B, d.Npad, d.nsplit, d.f32, d.fuse);
-}
-
+// (the standalone encoder takes the caller's dense M: make_dims' dense_m_caller)
 size_t pdsc_encoder_workspace_bytes(const pdsc_config *cfg, int32_t B, int32_t N) {
     Dims d;
-    if (check_cfg(cfg) != PDSC_OK || make_dims(cfg, B, N, d) != PDSC_OK) return 0;
-    dims_dense_m(d);
+    if (check_cfg(cfg) != PDSC_OK || make_dims(cfg, B, N, d, true) != PDSC_OK) return 0;
     Carve c(nullptr);
     carve_encoder(c, d);
     return c.off;
@@ -626,19 +581,18 @@ int32_t pdsc_encoder_f32(const pdsc_config *cfg, const float *packed, const floa
                          void *ws, size_t ws_bytes, pdsc_stream_t stream) {
     RET_IF(check_cfg(cfg));
     Dims d;
-    RET_IF(make_dims(cfg, B, N, d));
-    dims_dense_m(d);
+    RET_IF(make_dims(cfg, B, N, d, true));
     if (!packed || !corr_pos || !M || !normed || !conf || !ws) return fail(PDSC_ERR_ARG, "null pointer");
     RET_IF(need_ws(ws_bytes, pdsc_encoder_workspace_bytes(cfg, B, N)));
     Carve c(ws);
     const EncBufs e = carve_encoder(c, d);
     const PackLayout lay = make_layout(cfg->num_layers, cfg->in_dim);
-    return run_encoder(lay, packed, corr_pos, M, M_DENSE, d, e, feat, normed, nullptr, conf, S_(stream));
+    return run_encoder(lay, packed, corr_pos, M, d, e, feat, normed, nullptr, conf, S_(stream));
 }
 
 size_t pdsc_attention_workspace_bytes(int32_t B, int32_t N, int32_t C, int32_t precision) {
     if (C != CH || B < 1 || N < 1 || (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)) return 0;
-    const int Npad = round_up(N, QB), ns = attention_nsplit(B, N, precision == PDSC_PRECISION_F32);
+    const int Npad = round_up(N, QB), ns = plan_encoder(B, N, precision == PDSC_PRECISION_F32, true, false).nsplit;
     Carve c(nullptr);
     for (int i = 0; i < 3; ++i) c.take<_Float16>((size_t)2 * B * Npad * CH);
     c.take<float>((size_t)B * Npad * CH * ns);
@@ -658,7 +612,8 @@ int32_t pdsc_attention_f32(const float *q, const float *k, const float *v, const
     RET_IF(need_ws(ws_bytes, pdsc_attention_workspace_bytes(B, N, C, precision)));
     hipStream_t s = S_(stream);
     const bool f32 = precision == PDSC_PRECISION_F32;
-    const int Npad = round_up(N, QB), ns = attention_nsplit(B, N, f32);
+    const EncoderPlan plan = plan_encoder(B, N, f32, true, false);  // the split launch on the caller's dense M
+    const int Npad = plan.Npad, ns = plan.nsplit;
     Carve c(ws);
     _Float16 *qs = c.take<_Float16>((size_t)2 * B * Npad * CH);
     _Float16 *ks = c.take<_Float16>((size_t)2 * B * Npad * CH);
@@ -673,7 +628,7 @@ int32_t pdsc_attention_f32(const float *q, const float *k, const float *v, const
     } else {  // the caller's fp32 [B][N][C] rows -> the kernel's padded fp16 hi/lo layouts
         HIPCHK(launch_split_qkv(q, k, v, B, N, N, Npad, qs, ks, vs, vexp, s));
     }
-    HIPCHK(launch_attention(qs, ks, vs, vexp, M, M_DENSE, false, f32, B, N, Npad, ns, op, ml, s));
+    HIPCHK(launch_attention(plan, qs, ks, vs, vexp, M, op, ml, s));
     HIPCHK(launch_attn_combine(op, ml, f32, B, N, Npad, ns, msg, s));
     return PDSC_OK;
 }
@@ -707,9 +662,9 @@ int32_t pdsc_attention_layout(int32_t B, int32_t N, int32_t precision, int32_t *
     if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
         return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
     if (B < 1 || N < 1 || !Npad || !nsplit) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    *Npad = round_up(N, QB);
-    const bool f32 = precision == PDSC_PRECISION_F32;
-    *nsplit = attention_nsplit(B, N, f32, !attention_fused(B, N, f32) && attention_w64(B, N, f32));
+    const EncoderPlan plan = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false);
+    *Npad = plan.Npad;
+    *nsplit = plan.nsplit;
     return PDSC_OK;
 }
 
@@ -717,8 +672,8 @@ int32_t pdsc_encoder_plan(int32_t B, int32_t N, int32_t precision, int32_t *fuse
     if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
         return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
     if (B < 1 || N < 1 || !fused) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    const bool f32 = precision == PDSC_PRECISION_F32, fu = attention_fused(B, N, f32);
-    *fused = fu ? 1 : (attention_w64(B, N, f32) ? 2 : 0);
+    const EncoderPlan plan = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false);
+    *fused = plan.fused() ? 1 : (plan.w64() ? 2 : 0);
     return PDSC_OK;
 }
 
@@ -912,14 +867,13 @@ static int32_t forward_testing_impl(const pdsc_config *cfg, const float *packed,
     // a1 (:150-153).  (r04: a1 on a second stream beside the encoder's first
     // launch measured no gain at 128 x 1000 / 8 x 5000 and +44 us per single
     // pair -- the cross-stream event pair -- so the forward stays on one stream.)
-    const int mlay = forward_m_layout(d);
-    if (mlay == M_PACKED)
+    if (d.plan.m_layout == M_PACKED)
         HIPCHK(launch_compat_packed(src, tgt, d.B, d.N, sigma_d, f.M, s, rg));
     else
         HIPCHK(launch_compat(src, tgt, d.B, d.N, sigma_d, f.M, s, rg));
     STAGE(1);
     // a2-a4 (:155-156, :171)
-    RET_IF(run_encoder_fwd(lay, packed, corr_pos, f.M, mlay, d, f.enc, f.normed, f.normed_s, f.conf, s, rg, halves,
+    RET_IF(run_encoder_fwd(lay, packed, corr_pos, f.M, d, f.enc, f.normed, f.normed_s, f.conf, s, rg, halves,
                            bounds, parts));
     STAGE(2);
     // a5 (:174)
@@ -1011,12 +965,11 @@ int32_t pdsc_forward_training(const pdsc_config *cfg, const float *packed, const
     const PackLayout lay = make_layout(cfg->num_layers, cfg->in_dim);
     const float *sigma = packed + lay.sigma, *sigma_d = packed + lay.sigma_d;
     // a1-a4 as in testing (:150-156, :171)
-    const int mlay = forward_m_layout(d);
-    if (mlay == M_PACKED)
+    if (d.plan.m_layout == M_PACKED)
         HIPCHK(launch_compat_packed(src, tgt, d.B, d.N, sigma_d, f.M, s));
     else
         HIPCHK(launch_compat(src, tgt, d.B, d.N, sigma_d, f.M, s));
-    RET_IF(run_encoder(lay, packed, corr_pos, f.M, mlay, d, f.enc, nullptr, f.normed, f.normed_s, f.conf, s));
+    RET_IF(run_encoder(lay, packed, corr_pos, f.M, d, f.enc, nullptr, f.normed, f.normed_s, f.conf, s));
     // the loss's feature-similarity M (:158-163)
     if (M_out)
         HIPCHK(launch_feat_sim(d.f32 ? static_cast<const void *>(f.normed) : static_cast<const void *>(f.normed_s),

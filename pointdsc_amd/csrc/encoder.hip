@@ -23,9 +23,11 @@
 // -inf) exactly as :41; online softmax with a lazily re-based running max;
 // split-K over keys when B*N is too small to fill 256 CUs.
 #include <cstdlib>
+#include <type_traits>
 
 #include "attention.hpp"
 #include "attention_h3.hpp"
+#include "attention_plan.hpp"
 #include "attention_w64.hpp"
 
 namespace pdsc {
@@ -128,236 +130,178 @@ hipError_t launch_copy(const float *src, float *dst, int n, hipStream_t s) {
 // workgroup, XCD-aware block map.  (tools/attn_bench.hip A/B-times it against
 // the exact-fp32-MFMA kernel of attention.hpp.)
 constexpr int ATT_NW = 4;
-
-// Resident workgroups per round of the split-K decomposition (2 per CU on 256
-// CUs; attention_split_count).  A/B knob, measurement only: PDSC_ATT_TARGET
-// overrides it for the whole process.  (The exact-fp32 attention keeps its
-// round-2 rule: splits = ceil(target / blocks).)
-static int att_target() {
-    static const int t = [] {
-        const char *e = getenv("PDSC_ATT_TARGET");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 ? v : 512;
-    }();
-    return t;
-}
-// Waves (x 32 queries) per workgroup of the h3 split-K attention: 4, except 2
-// for batches of at most 16 blocks of 128 queries (single pairs up to N = 2048),
-// whose launch is latency-bound: twice the query blocks, each workgroup's K/V
-// stream shared by 2 waves.  Measured (ms per forward, two A/B rounds on one
-// box, profiles/r06_ab_att_nw.log): 1 x 1000 0.4235 -> 0.417, 1 x 2000 0.531 ->
-// 0.504, 1 x 5000 (not covered) equal; 1 wave 0.4185 / 0.515.  A/B knob
-// PDSC_ATT_NW=1|2|4 (measurement only) sets the small-batch count.
-static bool att_tiny(int B, int N);
-static int att_nw(int B, int N) {
-    static const int v = [] {
-        const char *e = getenv("PDSC_ATT_NW");
-        const int w = e ? atoi(e) : 2;
-        return (w == 1 || w == 2) ? w : ATT_NW;
-    }();
-    if (att_tiny(B, N)) return 1;
-    return (long)B * ((N + QB - 1) / QB) <= 16 ? v : ATT_NW;
-}
-// The smallest batches (at most 16 query blocks of 128 and splits of <= 24 key
-// tiles: a single pair to N = 1536, two to 1024, four to 512): 32-query workgroups whose key splits fill ONE round of
-// att_tiny_slots() (128) workgroups (a 1000-key pair: 32 blocks x 4 splits of 8
-// tiles, run by attention_h3_ws_kernel's 4 waves) instead of 16 blocks x 16
-// splits of 2 -- a quarter of the split partials, so pw_mid combines them
-// itself (use_precombine: fewer than 16 splits) and the combine_rows launch goes.
-// A/B knob PDSC_ATT_TINY=0 (measurement only).
-static int att_tiny_slots();
-static bool att_tiny(int B, int N) {
-    static const int lim = [] {  // PDSC_ATT_TINY=0: off; =n: up to n blocks of 128 queries (measurement only)
-        const char *e = getenv("PDSC_ATT_TINY");
-        return e ? atoi(e) : 16;
-    }();
-    if ((long)B * ((N + QB - 1) / QB) > lim) return false;
-    // splits of at most 24 key tiles (6 per wave of the wave-split kernel): ms per
-    // forward, 8 -> 16-block limit (profiles/r06_ab_tiny16.log): 2 x 1000 0.431 ->
-    // 0.382, 4 x 500 0.374 -> 0.324, 1 x 1500 (24 tiles) 0.456 -> 0.439, but 1 x 2000
-    // (32 tiles) 0.489 -> 0.504, which keeps the two-wave split plan
-    return attention_h3_grid<1>(B, N, std::min(att_target(), att_tiny_slots())).sps <= 24;
-}
-// The tiny plan's waves per workgroup splitting each key split's tiles
-// (attention_h3_ws_kernel): 4 (default), 2, or 1 = the one-wave kernel.
-// A/B knob PDSC_ATT_WS (measurement only).
-static int att_ws() {
-    static const int v = [] {
-        const char *e = getenv("PDSC_ATT_WS");
-        const int w = e ? atoi(e) : 4;
-        return (w == 1 || w == 2) ? w : 4;
-    }();
-    return v;
-}
-// The tiny plan's slot target (one round of this many workgroups): 128 (ms per
-// forward, wave-split kernel, profiles/r06_ab_tiny_slots.log: 1 x 1000 0.374 at
-// 256 slots -> 0.366 at 128 (4 splits of 8 tiles, 2 per wave; half the partials
-// again) -> 0.385 at 96, 0.415 at 64; 2 x 500 0.342 -> 0.316; 1 x 700 0.362 ->
-// 0.345).  A/B knob PDSC_ATT_TINY_SLOTS (measurement only).
-static int att_tiny_slots() {
-    static const int v = [] {
-        const char *e = getenv("PDSC_ATT_TINY_SLOTS");
-        const int x = e ? atoi(e) : 0;
-        return x > 0 ? x : 128;
-    }();
-    return v;
-}
-static AttnGridH3 prod_grid(int B, int N) {
-    if (att_tiny(B, N)) return attention_h3_grid<1>(B, N, std::min(att_target(), att_tiny_slots()));
-    switch (att_nw(B, N)) {
-    case 1: return attention_h3_grid<1>(B, N, att_target());
-    case 2: return attention_h3_grid<2>(B, N, att_target());
-    default: return attention_h3_grid<ATT_NW>(B, N, att_target());
-    }
-}
-
-// The attention's workgroup order, reversed on alternate layers (fused and
-// split-K launches; the stream-K form excepted): a launch
-// starts on the pairs whose M (and featL) the previous one read last, while
-// they may still sit in the Infinity Cache.  A/B knob PDSC_ZIGZAG=0 (measurement
-// only).
-static int zigzag_rev(int layer) {
-    static const int mode = [] {
-        const char *e = getenv("PDSC_ZIGZAG");
-        return e ? atoi(e) : 1;
-    }();
-    return mode == 0 ? 0 : mode == 2 ? !(layer & 1) : (layer & 1);
-}
-
 // PDSC_PRECISION_F32: attention.hpp's exact-fp32 MFMA kernel, 32-key stages, libm expf
 constexpr int ATT_F32_KTS = 32;
-static AttnGrid f32_grid(int B, int N) { return attention_grid<ATT_NW, ATT_F32_KTS>(B, N, att_target()); }
 
-// The 64-query-wave attention (attention_w64.hpp, one 4-wave workgroup per CU,
-// symmetric-packed M) for the split path: from 128 blocks of 256 queries
-// (8 x 5000: 160 blocks, 3 key splits).  Knob PDSC_W64: 0 never, 1 wherever the
-// split path runs (measurement only).
-static AttnGridH3 w64_grid(int B, int N) { return attention_w64_grid(B, N, att_target() / 2); }
-bool attention_w64(int B, int N, bool f32) {
-    static const int mode = [] {
-        const char *e = getenv("PDSC_W64");
-        return e ? atoi(e) : 2;
-    }();
-    if (f32 || mode == 0) return false;
-    return mode == 1 || (long)B * ((N + W64_QPB - 1) / W64_QPB) >= 128;
-}
-
-// Stream-K workgroups for a uniform batch on the w64 path (attention_w64_sk_kernel,
-// one per CU), or 0 for the split grid: when one round of nwg workgroups of
-// ceil(T / nwg) tiles (+ ~2 tiles for a workgroup's second segment) beats the
-// split grid's rounds of sps tiles.  Knob PDSC_W64_SK=0: never (measurement only).
-static int w64_sk_wgs(int B, int N) {
-    static const int mode = [] {
-        const char *e = getenv("PDSC_W64_SK");
-        return e ? atoi(e) : 1;
-    }();
-    if (!mode) return 0;
-    const int nwg = att_target() / 2;
-    const AttnGridH3 g = w64_grid(B, N);
+// The encoder's attention plan (attention_plan.hpp): every rule that picks a
+// kernel and its grid for a shape, each with the measurements behind it.
+EncoderPlan plan_encoder(int B, int N, bool f32, bool dense_m_caller, bool allow_fused) {
+    const AttnKnobs &k = attn_knobs();
+    EncoderPlan p{};
+    p.B = B;
+    p.N = N;
+    p.Npad = round_up(N, QB);
+    p.f32 = f32;
+    p.nw = ATT_NW;
+    p.ws = 1;
     const int nst = (N + H3_TILE - 1) / H3_TILE;
-    const long T = (long)B * g.nqb * nst, rounds = ((long)B * g.nqb * g.nsplit + nwg - 1) / nwg;
-    return T >= 4L * nwg && (T + nwg - 1) / nwg + 2 < rounds * g.sps ? nwg : 0;
-}
-// the w64 plan's partial slots: the split grid's, or the stream-K segments' if more
-static int w64_nsplit(int B, int N) {
-    const AttnGridH3 g = w64_grid(B, N);
-    const int nwg = w64_sk_wgs(B, N);
-    return nwg ? std::max(g.nsplit, w64_sk_nsplit(B, g.nqb, (N + H3_TILE - 1) / H3_TILE, nwg)) : g.nsplit;
-}
+    const long blocks = (long)B * ((N + QB - 1) / QB);  // of 128 queries
+    auto take = [&p](AttnKind kind, const auto &g) {
+        p.kind = kind;
+        p.nqb = g.nqb;
+        p.sps = g.sps;
+        p.nsplit = g.nsplit;
+    };
 
-int attention_nsplit(int B, int N, bool f32, bool w64) {
-    return f32 ? f32_grid(B, N).nsplit : (w64 ? w64_nsplit(B, N) : prod_grid(B, N).nsplit);
-}
+    // attn_pw2 wherever pw2 runs and the attention has one key split
+    const AttnGridH3 fg = attention_h3_grid<PW2_W>(B, N, k.target * 4 / PW2_W);
+    const bool fused = allow_fused && k.fuse && use_pw2(B, p.Npad, f32) && fg.nsplit == 1 && fg.nqb * PW2_PTS == p.Npad;
 
-template <int NW>
-static hipError_t launch_attention_h3(const _Float16 *qs, const _Float16 *ks, const _Float16 *vs, const float *vexp,
-                                      const float *M, bool m_packed, const AttnGridH3 &g, float *opart, float *ml,
-                                      hipStream_t s) {
-    const dim3 grid(g.B * g.nqb * g.nsplit), block(NW * 64);
-    const size_t lds = attention_h3_lds_bytes<NW>();
-    if (g.sps >= 3) {  // long splits: the early-issue loop (attention_h3_core's EARLY)
-        if (m_packed)
-            hipLaunchKernelGGL((attention_h3_kernel<NW, true, true, true>), grid, block, lds, s, qs, ks, vs, vexp, M, g,
-                               opart, ml);
-        else
-            hipLaunchKernelGGL((attention_h3_kernel<NW, true, false, true>), grid, block, lds, s, qs, ks, vs, vexp, M, g,
-                               opart, ml);
-    } else if (m_packed)
-        hipLaunchKernelGGL((attention_h3_kernel<NW, true, true>), grid, block, lds, s, qs, ks, vs, vexp, M, g, opart, ml);
-    else
-        hipLaunchKernelGGL((attention_h3_kernel<NW, true, false>), grid, block, lds, s, qs, ks, vs, vexp, M, g, opart, ml);
-    return hipGetLastError();
-}
-
-hipError_t launch_attention(const void *q, const void *k, const void *v, const float *vexp, const float *M,
-                            int m_layout, bool w64, bool f32, int B, int N, int Npad, int nsplit, float *opart,
-                            float *ml, hipStream_t s, Ragged rg, int layer) {
-    const bool m_packed = m_layout == M_PACKED;
-    if (w64) {  // attention_w64 (H3 layouts, symmetric-packed M)
-        if (f32 || !m_packed) return hipErrorInvalidValue;
-        AttnGridH3 g = w64_grid(B, N);
-        if (g.Npad != Npad || nsplit != w64_nsplit(B, N)) return hipErrorInvalidValue;
-        g.nsplit = nsplit;  // slots past the split grid's own: empty splits (st0 >= st1)
-        const int nwg = rg.nv && !rg.eq ? 0 : w64_sk_wgs(B, N);
-        if (nwg) {
-            hipLaunchKernelGGL((attention_w64_sk_kernel<true>), dim3(nwg), dim3(W64_NW * 64), W64_LDS, s,
-                               static_cast<const _Float16 *>(q), static_cast<const _Float16 *>(k),
-                               static_cast<const _Float16 *>(v), vexp, M, g, nwg, opart, ml);
-            return hipGetLastError();
+    // The 64-query-wave attention (attention_w64.hpp, one 4-wave workgroup per CU,
+    // symmetric-packed M) for the split path: from 128 blocks of 256 queries
+    // (8 x 5000: 160 blocks, 3 key splits).
+    const bool w64 = !fused && !f32 && !dense_m_caller && k.w64 != 0 &&
+                     (k.w64 == 1 || (long)B * ((N + W64_QPB - 1) / W64_QPB) >= 128);
+    if (f32) {
+        take(ATT_F32, attention_grid<ATT_NW, ATT_F32_KTS>(B, N, k.target));
+    } else if (w64) {
+        const int nwg = k.target / 2;
+        const AttnGridH3 g = attention_w64_grid(B, N, nwg);
+        take(ATT_W64, g);
+        // Stream-K (one workgroup per CU) for a uniform batch: when one round of nwg
+        // workgroups of ceil(T / nwg) tiles (+ ~2 tiles for a workgroup's second
+        // segment) beats the split grid's rounds of sps tiles.
+        const long T = (long)B * g.nqb * nst, rounds = ((long)B * g.nqb * g.nsplit + nwg - 1) / nwg;
+        if (k.w64_sk && T >= 4L * nwg && (T + nwg - 1) / nwg + 2 < rounds * g.sps) {
+            p.kind = ATT_W64_SK;
+            p.sk_wgs = nwg;
+            p.nsplit = std::max(g.nsplit, w64_sk_nsplit(B, g.nqb, nst, nwg));
         }
-        g.nv = rg.nv;
-        g.po = rg.po;
-        g.rev = rg.po ? 0 : zigzag_rev(layer);
-        hipLaunchKernelGGL((attention_w64_kernel<true>), dim3(g.B * g.nqb * g.nsplit), dim3(W64_NW * 64), W64_LDS, s,
-                           static_cast<const _Float16 *>(q), static_cast<const _Float16 *>(k),
-                           static_cast<const _Float16 *>(v), vexp, M, g, opart, ml);
-        return hipGetLastError();
+    } else {
+        // The smallest batches (at most 16 query blocks of 128 and splits of <= 24 key
+        // tiles: a single pair to N = 1536, two to 1024, four to 512): 32-query
+        // workgroups whose key splits fill ONE round of tiny_slots (128) workgroups (a
+        // 1000-key pair: 32 blocks x 4 splits of 8 tiles, run by attention_h3_ws_kernel's
+        // 4 waves) instead of 16 blocks x 16 splits of 2 -- a quarter of the split
+        // partials, so pw_mid combines them itself (precombine: fewer than 16 splits)
+        // and the combine_rows launch goes.
+        // The slot target, 128 (ms per forward, wave-split kernel,
+        // profiles/r06_ab_tiny_slots.log): 1 x 1000 0.374 at 256 slots -> 0.366 at 128
+        // (4 splits of 8 tiles, 2 per wave; half the partials again) -> 0.385 at 96,
+        // 0.415 at 64; 2 x 500 0.342 -> 0.316; 1 x 700 0.362 -> 0.345.
+        // Splits of at most 24 key tiles (6 per wave of the wave-split kernel): ms per
+        // forward, 8 -> 16-block limit (profiles/r06_ab_tiny16.log): 2 x 1000 0.431 ->
+        // 0.382, 4 x 500 0.374 -> 0.324, 1 x 1500 (24 tiles) 0.456 -> 0.439, but 1 x 2000
+        // (32 tiles) 0.489 -> 0.504, which keeps the two-wave split plan.
+        const AttnGridH3 tg = attention_h3_grid<1>(B, N, std::min(k.target, k.tiny_slots));
+        if (blocks <= k.tiny && tg.sps <= 24) {
+            // The tiles spread over the workgroup's waves where each split has at least
+            // 4 tiles (measured, ms per forward, 1 -> 4 waves: 1 x 1000 (4 tiles per
+            // split) 0.393 -> 0.377; 1 x 700 (2 tiles) 0.366 -> 0.371, 2 x 500 0.347 ->
+            // 0.351, so shorter splits keep the one-wave kernel; profiles/r06_ab_att_ws.log).
+            const bool wave_split = k.ws > 1 && tg.sps >= 4;
+            take(wave_split ? ATT_H3_WS : ATT_H3, tg);
+            p.nw = 1;
+            p.ws = wave_split ? k.ws : 1;
+        } else {
+            // Waves (x 32 queries) per workgroup: 4, except 2 for batches of at most 16
+            // blocks of 128 queries (single pairs up to N = 2048), whose launch is
+            // latency-bound: twice the query blocks, each workgroup's K/V stream shared
+            // by 2 waves.  Measured (ms per forward, two A/B rounds on one box,
+            // profiles/r06_ab_att_nw.log): 1 x 1000 0.4235 -> 0.417, 1 x 2000 0.531 ->
+            // 0.504, 1 x 5000 (not covered) equal; 1 wave 0.4185 / 0.515.
+            p.nw = blocks <= 16 ? k.nw : ATT_NW;
+            take(ATT_H3, p.nw == 1   ? attention_h3_grid<1>(B, N, k.target)
+                         : p.nw == 2 ? attention_h3_grid<2>(B, N, k.target)
+                                     : attention_h3_grid<ATT_NW>(B, N, k.target));
+        }
+        // long splits: the early-issue loop (attention_h3_core's EARLY; measured there)
+        p.early = p.kind == ATT_H3 && p.sps >= 3;
     }
-    if (f32) {  // fp32 [B][Npad][CH] rows, dense M
-        AttnGrid g = f32_grid(B, N);
-        g.nv = rg.nv;
-        if (m_packed || g.Npad != Npad || g.nsplit != nsplit) return hipErrorInvalidValue;
-        const size_t lds = attention_lds_bytes<ATT_NW, ATT_F32_KTS>();
-        hipLaunchKernelGGL((attention_kernel_t<ATT_NW, ATT_F32_KTS, false, true>), dim3(g.B * g.nqb * g.nsplit),
-                           dim3(ATT_NW * 64), lds, s,
-                           static_cast<const float *>(q), static_cast<const float *>(k),
-                           static_cast<const float *>(v), M, g, opart, ml);
-        return hipGetLastError();
+
+    // The tiniest batches (<= 16 query blocks of 128, >= 16 key splits: a single
+    // N = 2000 pair) combine the attention partials in their own launch
+    // (combine_rows) rather than in the pointwise kernel's prologue: measured
+    // 0.511 -> 0.482 ms per single-pair forward (N = 1000, before the tiny plan),
+    // but slower from 4 pairs of N = 1000 on (an extra launch per layer).
+    p.precombine = k.precombine && !f32 && !fused && p.nsplit >= 16 && blocks <= 16;
+    // M: symmetric-packed for the H3 plans, dense for exact fp32, for a caller's
+    // own M, and under PDSC_DENSE_M=1 on the h3 plans other than attention_w64's.
+    p.m_layout = w64 || !(f32 || dense_m_caller || k.dense_m) ? M_PACKED : M_DENSE;
+
+    if (fused) {  // one key split per query block; nsplit stays the split plan's
+        p.kind = ATT_FUSED;
+        p.nw = PW2_W;
+        p.ws = 1;
+        p.early = false;
+        p.nqb = fg.nqb;
+        p.sps = nst;
     }
+    return p;
+}
+
+// the h3 kernels' grid argument for layer `layer` (stream-K: the uniform batch's form)
+static AttnGridH3 plan_grid_h3(const EncoderPlan &plan, const Ragged &rg, int layer) {
+    const bool sk = plan.kind == ATT_W64_SK;
+    return AttnGridH3{plan.B, plan.N, plan.Npad, plan.nqb, plan.fused() ? 1 : plan.nsplit, plan.sps,
+                      sk ? nullptr : rg.nv, sk ? nullptr : rg.po, plan.rev(rg, layer)};
+}
+
+// A run-time bool / int of the plan as a kernel template argument: f(std::bool_constant) / f(std::integral_constant).
+template <typename F> static void with_bool(bool b, F &&f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+template <int V, int... Vs, typename F> static void with_int(int v, F &&f) {
+    if (v == V) f(std::integral_constant<int, V>{});
+    else if constexpr (sizeof...(Vs) > 0) with_int<Vs...>(v, f);
+}
+
+// One layer's attention as the plan says.
+hipError_t launch_attention(const EncoderPlan &plan, const void *q, const void *k, const void *v, const float *vexp,
+                            const float *M, float *opart, float *ml, hipStream_t s, Ragged rg, int layer) {
+    const dim3 grid(plan.workgroups());
     const _Float16 *qs = static_cast<const _Float16 *>(q), *ks = static_cast<const _Float16 *>(k),
                    *vs = static_cast<const _Float16 *>(v);
-    AttnGridH3 g = prod_grid(B, N);
-    g.nv = rg.nv;
-    g.po = rg.po;
-    g.rev = rg.po ? 0 : zigzag_rev(layer);
-    if (g.Npad != Npad || g.nsplit != nsplit) return hipErrorInvalidValue;
-    const int nw = att_nw(B, N);
-    // the tiny plan's tiles spread over the workgroup's waves where each split has
-    // at least 4 tiles (measured, ms per forward, 1 -> 4 waves: 1 x 1000 (4 tiles per
-    // split) 0.393 -> 0.377; 1 x 700 (2 tiles) 0.366 -> 0.371, 2 x 500 0.347 -> 0.351,
-    // so shorter splits keep the one-wave kernel; profiles/r06_ab_att_ws.log)
-    if (att_tiny(B, N) && att_ws() > 1 && g.sps >= 4) {
-        const dim3 grid(g.B * g.nqb * g.nsplit);
-        if (att_ws() == 2) {
-            if (m_packed)
-                hipLaunchKernelGGL((attention_h3_ws_kernel<2, true>), grid, dim3(128), attention_h3_ws_lds_bytes<2>(), s,
-                                   qs, ks, vs, vexp, M, g, opart, ml);
-            else
-                hipLaunchKernelGGL((attention_h3_ws_kernel<2, false>), grid, dim3(128), attention_h3_ws_lds_bytes<2>(),
-                                   s, qs, ks, vs, vexp, M, g, opart, ml);
-        } else {
-            if (m_packed)
-                hipLaunchKernelGGL((attention_h3_ws_kernel<4, true>), grid, dim3(256), attention_h3_ws_lds_bytes<4>(), s,
-                                   qs, ks, vs, vexp, M, g, opart, ml);
-            else
-                hipLaunchKernelGGL((attention_h3_ws_kernel<4, false>), grid, dim3(256), attention_h3_ws_lds_bytes<4>(),
-                                   s, qs, ks, vs, vexp, M, g, opart, ml);
-        }
-        return hipGetLastError();
+    const AttnGridH3 g = plan_grid_h3(plan, rg, layer);
+    const bool packed = plan.m_layout == M_PACKED;
+    switch (plan.kind) {
+    case ATT_W64_SK:
+        hipLaunchKernelGGL((attention_w64_sk_kernel<true>), grid, dim3(W64_NW * 64), W64_LDS, s, qs, ks, vs, vexp, M, g,
+                           plan.sk_wgs, opart, ml);
+        break;
+    case ATT_W64:
+        hipLaunchKernelGGL((attention_w64_kernel<true>), grid, dim3(W64_NW * 64), W64_LDS, s, qs, ks, vs, vexp, M, g,
+                           opart, ml);
+        break;
+    case ATT_F32: {  // fp32 [B][Npad][CH] rows, dense M
+        const AttnGrid gf{plan.B, plan.N, plan.Npad, plan.nqb, plan.nsplit, plan.sps, rg.nv};
+        hipLaunchKernelGGL((attention_kernel_t<ATT_NW, ATT_F32_KTS, false, true>), grid, dim3(ATT_NW * 64),
+                           (attention_lds_bytes<ATT_NW, ATT_F32_KTS>()), s, static_cast<const float *>(q),
+                           static_cast<const float *>(k), static_cast<const float *>(v), M, gf, opart, ml);
+        break;
     }
-    if (nw == 1) return launch_attention_h3<1>(qs, ks, vs, vexp, M, m_packed, g, opart, ml, s);
-    if (nw == 2) return launch_attention_h3<2>(qs, ks, vs, vexp, M, m_packed, g, opart, ml, s);
-    return launch_attention_h3<ATT_NW>(qs, ks, vs, vexp, M, m_packed, g, opart, ml, s);
+    case ATT_H3_WS:
+        with_int<2, 4>(plan.ws, [&](auto ws) {
+            with_bool(packed, [&](auto pk) {
+                constexpr int WS = decltype(ws)::value;
+                hipLaunchKernelGGL((attention_h3_ws_kernel<WS, decltype(pk)::value>), grid, dim3(WS * 64),
+                                   attention_h3_ws_lds_bytes<WS>(), s, qs, ks, vs, vexp, M, g, opart, ml);
+            });
+        });
+        break;
+    case ATT_H3:
+        with_int<1, 2, ATT_NW>(plan.nw, [&](auto nw) {
+            with_bool(plan.early, [&](auto early) {
+                with_bool(packed, [&](auto pk) {
+                    constexpr int NW = decltype(nw)::value;
+                    hipLaunchKernelGGL((attention_h3_kernel<NW, true, decltype(pk)::value, decltype(early)::value>), grid,
+                                       dim3(NW * 64), attention_h3_lds_bytes<NW>(), s, qs, ks, vs, vexp, M, g, opart,
+                                       ml);
+                });
+            });
+        });
+        break;
+    default: return hipErrorInvalidValue;  // ATT_FUSED: launch_attn_pw2
+    }
+    return hipGetLastError();
 }
 
 // fp32 rows [B][N][CH] -> [B][Npad][CH] with zero padding rows (the f32 attention's input)
@@ -1304,9 +1248,8 @@ __global__ __launch_bounds__(256, 2) void pw_last_kernel(
 // epilogue coefficients (bias, BN alpha / beta) sit in LDS for the launch.
 // Two workgroups per CU (~55 KiB of LDS and <= 256 VGPRs each) overlap one's
 // HBM phases and epilogues with the other's MFMAs.
-#ifndef PW2_WAVES
-#define PW2_WAVES 4
-#endif
+// (PW2_W waves x 32 = PW2_PTS points per workgroup: attention_plan.hpp, whose fused
+// rule depends on them; build knob -DPW2_WAVES.)
 // The fused kernels' attention with attention_h3_core's early-issue loop
 // (measured, one box: 128 x 1000 forward 3.802 vs 3.831 ms over three A/B
 // pairs, attn_pw2 290.3 vs 291.7 us; ragged 4.51 vs 4.58 ms).  A/B build
@@ -1314,7 +1257,6 @@ __global__ __launch_bounds__(256, 2) void pw_last_kernel(
 #ifndef PW2_EARLY
 #define PW2_EARLY 1
 #endif
-constexpr int PW2_W = PW2_WAVES;                      // waves per workgroup (32 points each)
 constexpr int PW2_OCC = PW2_W >= 8 ? 1 : 2;           // workgroups per CU (<= 256 VGPRs: 2 waves per SIMD)
 // 16 two-plane blocks = 32 KiB chunks (r04, A/B: -0.7 % per step at 128 x 1000
 // against 8, equal at 8 x 5000 and one pair): half the chunk barriers per chain
@@ -1324,7 +1266,6 @@ constexpr int PW2_OCC = PW2_W >= 8 ? 1 : 2;           // workgroups per CU (<= 2
 constexpr int PW2_CB = PW2_CHUNK_BLOCKS;              // blocks per chunk (W_PLANES KiB each)
 constexpr int PW2_BLKB = W_PLANES * 1024;             // bytes per block (W_PLANES planes)
 constexpr int PW2_SLOT = PW2_CB * PW2_BLKB;
-constexpr int PW2_PTS = PW2_W * 32;
 constexpr int PW2_COEF = 1536;                        // floats of epilogue coefficients in LDS
 constexpr int PW2_NSLOT = 2;                          // weight-ring slots
 constexpr size_t PW2_LDS = PW2_NSLOT * PW2_SLOT + PW2_COEF * sizeof(float);
@@ -1973,20 +1914,6 @@ __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void attn_pw2_last_kernel(
 }
 #undef PW2_PROLOGUE
 
-// pw2 for launches of at least 320 128-point workgroups, 1.25 per CU (knob
-// PDSC_PW2: 0 never, 2 always, else this rule; measurement only).  Measured
-// encoder ms, pw2 vs pw_mid chains: 8 x N=5000 (320 WGs; 3 key splits) 4.48
-// vs 4.61; 40 x 1000 (320, fused) 1.47 vs 1.78; 56 x 1000 (448, fused) 1.68 vs
-// 2.12; 32 x 1000 (256) 1.26 vs 1.22 and 1.24 fused; 16 x 1000 (128) 0.95 vs 0.80.
-static bool use_pw2(int B, int Npad, bool f32) {
-    static const int mode = [] {
-        const char *e = getenv("PDSC_PW2");
-        return e ? atoi(e) : 1;
-    }();
-    if (f32 || mode == 0) return false;
-    return mode == 2 || (long)B * ((Npad + PW2_PTS - 1) / PW2_PTS) >= 320;
-}
-
 static W2Sched sched_qkv(W2Sched S, const PwDense4 &d) {
     w2_sched_add(S, d.pcn, CH, CH);
     w2_sched_add(S, d.q, CH, CH);
@@ -2005,59 +1932,32 @@ static W2Sched sched_msg(const PwMsg &m) {
 static PwDense4 dense4(const LayerOff &l) { return PwDense4{l.pcn, l.q, l.k, l.v}; }
 static PwMsg msg3(const LayerOff &l) { return PwMsg{l.fc0, l.fc3, l.fc6}; }
 
-// attn_pw2 wherever pw2 runs and the attention has one key split (knob
-// PDSC_FUSE=0 keeps the two launches; measurement only).
-static AttnGridH3 fused_grid(int B, int N) { return attention_h3_grid<PW2_W>(B, N, att_target() * 4 / PW2_W); }
-// the fused launches' grid: one key split always (attention_fused chose the plan
-// on the whole batch; a part of it -- run_encoder_part's halves -- keeps it)
-static AttnGridH3 fused_launch_grid(int B, int N) {
-    AttnGridH3 g = fused_grid(B, N);
-    const int nst = (N + H3_TILE - 1) / H3_TILE;
-    g.sps = nst;
-    g.nsplit = 1;
-    return g;
-}
-bool attention_fused(int B, int N, bool f32) {
-    static const bool off = [] {
-        const char *e = getenv("PDSC_FUSE");
-        return e && e[0] == '0';
-    }();
-    const int Npad = round_up(N, QB);
-    const AttnGridH3 g = fused_grid(B, N);
-    return !off && use_pw2(B, Npad, f32) && g.nsplit == 1 && g.nqb * PW2_PTS == Npad;
-}
-
-hipError_t launch_attn_pw2(const float *packed, const PackLayout &lay, int layer, const void *q, const void *k,
-                           const void *v, const float *vexp_in, const float *M, bool m_packed, int B, int N, int Npad,
+// The fused launches (the plan's ATT_FUSED): one key split per query block, a
+// workgroup per PW2_PTS queries.
+hipError_t launch_attn_pw2(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
+                           const void *q, const void *k, const void *v, const float *vexp_in, const float *M,
                            float *feat, void *qo, void *ko, void *vo, float *vexp_out, hipStream_t s, Ragged rg) {
-    AttnGridH3 g = fused_launch_grid(B, N);
-    g.nv = rg.nv;
-    g.po = rg.po;
-    g.rev = rg.po ? 0 : zigzag_rev(layer);  // (ragged batches keep their longest-first order)
-    if (g.nsplit != 1 || g.Npad != Npad || g.nqb * PW2_PTS != Npad || layer + 1 >= lay.L) return hipErrorInvalidValue;
+    if (!plan.fused() || layer + 1 >= lay.L) return hipErrorInvalidValue;
+    const AttnGridH3 g = plan_grid_h3(plan, rg, layer);
     const W2Sched S = sched_qkv(sched_msg(msg3(lay.layer[layer])), dense4(lay.layer[layer + 1]));
     const size_t lds = std::max(attention_h3_lds_bytes<PW2_W>(), PW2_LDS);
     const _Float16 *qs = static_cast<const _Float16 *>(q), *ks = static_cast<const _Float16 *>(k),
                    *vs = static_cast<const _Float16 *>(v);
     _Float16 *Q = static_cast<_Float16 *>(qo), *K = static_cast<_Float16 *>(ko), *V = static_cast<_Float16 *>(vo);
-    if (m_packed)
-        hipLaunchKernelGGL(attn_pw2_kernel<true>, dim3(g.B * g.nqb), dim3(PW2_W * 64), lds, s, qs, ks, vs, vexp_in, M,
-                           g, packed, S, msg3(lay.layer[layer]), dense4(lay.layer[layer + 1]), feat, Q, K, V, vexp_out);
-    else
-        hipLaunchKernelGGL(attn_pw2_kernel<false>, dim3(g.B * g.nqb), dim3(PW2_W * 64), lds, s, qs, ks, vs, vexp_in, M,
-                           g, packed, S, msg3(lay.layer[layer]), dense4(lay.layer[layer + 1]), feat, Q, K, V, vexp_out);
+    with_bool(plan.m_layout == M_PACKED, [&](auto pk) {
+        hipLaunchKernelGGL(attn_pw2_kernel<decltype(pk)::value>, dim3(plan.workgroups()), dim3(PW2_W * 64), lds, s, qs,
+                           ks, vs, vexp_in, M, g, packed, S, msg3(lay.layer[layer]), dense4(lay.layer[layer + 1]), feat,
+                           Q, K, V, vexp_out);
+    });
     return hipGetLastError();
 }
 
-hipError_t launch_attn_pw2_last(const float *packed, const PackLayout &lay, const void *q, const void *k,
-                                const void *v, const float *vexp_in, const float *M, bool m_packed, int B, int N,
-                                int Npad, const float *feat, float *feat_out, float *normed, _Float16 *normed_s,
-                                float *conf, hipStream_t s, Ragged rg) {
-    AttnGridH3 g = fused_launch_grid(B, N);
-    g.nv = rg.nv;
-    g.po = rg.po;
-    g.rev = rg.po ? 0 : zigzag_rev(lay.L - 1);
-    if (g.nsplit != 1 || g.Npad != Npad || g.nqb * PW2_PTS != Npad) return hipErrorInvalidValue;
+hipError_t launch_attn_pw2_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const void *q,
+                                const void *k, const void *v, const float *vexp_in, const float *M, const float *feat,
+                                float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
+                                Ragged rg) {
+    if (!plan.fused()) return hipErrorInvalidValue;
+    const AttnGridH3 g = plan_grid_h3(plan, rg, lay.L - 1);
     W2Sched S = sched_msg(msg3(lay.layer[lay.L - 1]));
     w2_sched_add(S, lay.c0, CH, CLS);
     w2_sched_add(S, lay.c2, CLS, CLS);
@@ -2065,14 +1965,11 @@ hipError_t launch_attn_pw2_last(const float *packed, const PackLayout &lay, cons
     const _Float16 *qs = static_cast<const _Float16 *>(q), *ks = static_cast<const _Float16 *>(k),
                    *vs = static_cast<const _Float16 *>(v);
     const PwMsg m = msg3(lay.layer[lay.L - 1]);
-    if (m_packed)
-        hipLaunchKernelGGL(attn_pw2_last_kernel<true>, dim3(g.B * g.nqb), dim3(PW2_W * 64), lds, s, qs, ks, vs, vexp_in,
-                           M, g, packed, S, m, lay.c0, lay.c2, lay.c4_w, lay.c4_b, feat, feat_out, normed, normed_s,
-                           conf);
-    else
-        hipLaunchKernelGGL(attn_pw2_last_kernel<false>, dim3(g.B * g.nqb), dim3(PW2_W * 64), lds, s, qs, ks, vs,
-                           vexp_in, M, g, packed, S, m, lay.c0, lay.c2, lay.c4_w, lay.c4_b, feat, feat_out, normed,
-                           normed_s, conf);
+    with_bool(plan.m_layout == M_PACKED, [&](auto pk) {
+        hipLaunchKernelGGL(attn_pw2_last_kernel<decltype(pk)::value>, dim3(plan.workgroups()), dim3(PW2_W * 64), lds, s,
+                           qs, ks, vs, vexp_in, M, g, packed, S, m, lay.c0, lay.c2, lay.c4_w, lay.c4_b, feat, feat_out,
+                           normed, normed_s, conf);
+    });
     return hipGetLastError();
 }
 

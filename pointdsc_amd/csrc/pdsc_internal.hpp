@@ -173,32 +173,29 @@ hipError_t launch_copy(const float *src, float *dst, int n, hipStream_t s);
 // Attention partials for one layer: opart [B][nsplit][Npad x CH], ml [B][nsplit][Npad][2];
 // opart rows [Npad][CH] for f32, the fragment-block tiling of attention_h3.hpp
 // (h3_opart_off) for H3.
-// the split path's attention as attention_w64 (64-query waves) for this shape?
-bool attention_w64(int B, int N, bool f32);
-int attention_nsplit(int B, int N, bool f32, bool w64 = false);
 // M's layouts: dense [B][N][N], symmetric-packed (mpack_*)
 enum MLayout { M_DENSE = 0, M_PACKED = 1 };
+// The attention launchers launch what the call's plan says (attention_plan.hpp:
+// plan_encoder, then plan.for_ragged(rg) for a ragged batch).
+struct EncoderPlan;
 // q, k, v: the fp16 hi/lo split layouts of attention_h3.hpp (4 B per element),
-// or fp32 [B][Npad][CH] rows when f32 (exact-fp32 MFMA, attention.hpp).
-// M: dense [B][N][N] or symmetric-packed [B][mpack_floats(N)] (H3), per m_layout.
+// or fp32 [B][Npad][CH] rows for the exact-fp32 plan (attention.hpp).
+// M: dense [B][N][N] or symmetric-packed [B][mpack_floats(N)], per plan.m_layout.
 // vexp: [B][Npad/32] V-tile exponents of the H3 layout (attention_h3.hpp); unused for f32.
-// w64: attention_w64 (H3 and packed M only, nsplit from attention_nsplit(.., w64 = true)).
-hipError_t launch_attention(const void *q, const void *k, const void *v, const float *vexp, const float *M,
-                            int m_layout, bool w64, bool f32, int B, int N, int Npad, int nsplit, float *opart,
-                            float *ml, hipStream_t s, Ragged rg = {}, int layer = 0);
-// attention_l fused with pw_mid_l (encoder.hip: attn_pw2_kernel) for this shape?
-bool attention_fused(int B, int N, bool f32);
-// attention of layer `layer` on (q, k, v, vexp_in) + the pointwise chain to the
-// layer-(layer+1) (qo, ko, vo, vexp_out), H3 layouts; feat updated in place.
-hipError_t launch_attn_pw2(const float *packed, const PackLayout &lay, int layer, const void *q, const void *k,
-                           const void *v, const float *vexp_in, const float *M, bool m_packed, int B, int N, int Npad,
+hipError_t launch_attention(const EncoderPlan &plan, const void *q, const void *k, const void *v, const float *vexp,
+                            const float *M, float *opart, float *ml, hipStream_t s, Ragged rg = {}, int layer = 0);
+// The fused plan: attention of layer `layer` on (q, k, v, vexp_in) + the pointwise
+// chain to the layer-(layer+1) (qo, ko, vo, vexp_out), H3 layouts; feat updated in
+// place (encoder.hip: attn_pw2_kernel).
+hipError_t launch_attn_pw2(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
+                           const void *q, const void *k, const void *v, const float *vexp_in, const float *M,
                            float *feat, void *qo, void *ko, void *vo, float *vexp_out, hipStream_t s, Ragged rg = {});
-// attention of the last layer on (q, k, v, vexp_in) + its fc_message, residual,
+// The fused plan: attention of the last layer on (q, k, v, vexp_in) + its fc_message, residual,
 // F.normalize and classifier (encoder.hip: attn_pw2_last_kernel); outputs as launch_pw_last.
-hipError_t launch_attn_pw2_last(const float *packed, const PackLayout &lay, const void *q, const void *k,
-                                const void *v, const float *vexp_in, const float *M, bool m_packed, int B, int N,
-                                int Npad, const float *feat, float *feat_out, float *normed, _Float16 *normed_s,
-                                float *conf, hipStream_t s, Ragged rg = {});
+hipError_t launch_attn_pw2_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const void *q,
+                                const void *k, const void *v, const float *vexp_in, const float *M, const float *feat,
+                                float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
+                                Ragged rg = {});
 // fp32 rows [B][N][CH] -> [B][Npad][CH], padding rows zero.
 hipError_t launch_pad_rows(const float *x, int B, int N, int Npad, float *y, hipStream_t s);
 // fp32 q, k, v [B][ld][CH] -> split layouts (rows N..Npad-1 zero).
@@ -209,7 +206,7 @@ hipError_t launch_attn_combine(const float *opart, const float *ml, bool f32, in
                                int nsplit, float *msg, hipStream_t s);
 
 // Pointwise chains (one workgroup per PT points); q, k, v in launch_attention's layouts.
-// fused: the batch runs the fused plan (attention_fused), whatever B this call covers.
+// fused: the batch runs the fused plan (EncoderPlan::fused), whatever B this call covers.
 hipError_t launch_pw_first(const float *packed, const PackLayout &lay, const float *corr_pos, bool f32, int B,
                            int N, int Npad, float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s,
                            Ragged rg = {}, bool fused = false);
