@@ -175,6 +175,14 @@ int32_t pdsc_attention_layout(int32_t B, int32_t N, int32_t precision, int32_t *
  * and the attention is the 64-query-wave kernel (one 4-wave workgroup per CU,
  * attention_w64.hpp; the forward's M symmetric-packed as for plans 0/1).    */
 int32_t pdsc_encoder_plan(int32_t B, int32_t N, int32_t precision, int32_t *fused);
+/* *vfold = 1 when that plan folds fc_message[0] into the V projection (a
+ * 64-channel V' = (W0 Wv) x and P.V; the PDSC_VFOLD=0 knob: never), else 0.  */
+int32_t pdsc_encoder_plan_vfold(int32_t B, int32_t N, int32_t precision, int32_t *vfold);
+/* Where one dense block of a layer sits in the packed blob (tests, tools):
+ * block 0..7 = PointCN, fc_message 0 / 3 / 6, projection q / k / v, and the
+ * folded W0 Wv block; offsets (in floats) of its weights, bias, BatchNorm
+ * alpha and beta ([out] each) and scale {2^-s, 2^s}.                          */
+int32_t pdsc_packed_block(const pdsc_config *cfg, int32_t layer, int32_t block, size_t offsets[5]);
 
 /* Measurement hook (bench.py): while capacity > 0, every attention launch the
  * encoder issues from the calling thread records start_events[i] / stop_events[i]

@@ -144,7 +144,7 @@ int run_encoder(const PackLayout &lay, const float *packed, const float *corr_po
                 Ragged rg = {}) {
     const EncoderPlan plan = d.plan.for_ragged(rg);
     HIPCHK(launch_pw_first(packed, lay, corr_pos, d.f32, d.B, d.N, d.Npad, e.feat, e.q, e.k, e.v, e.vexp, s, rg,
-                           plan.fused()));
+                           plan.fused(), plan.vfold));
     if (plan.fused()) {  // every layer fused (0 .. L-2 with the next layer's PointCN/QKV, Q/K/V alternating between the two sets)
         _Float16 *q = e.q, *k = e.k, *v = e.v, *q2 = e.q2, *k2 = e.k2, *v2 = e.v2;
         float *vx = e.vexp, *vx2 = e.vexp2;
@@ -177,11 +177,11 @@ int run_encoder(const PackLayout &lay, const float *packed, const float *corr_po
         }
         if (l + 1 < lay.L) {
             HIPCHK(launch_pw_mid(packed, lay, l, d.f32, op, mlp, ns, d.B, d.N, d.Npad, feat, feat_alt, e.q, e.k, e.v,
-                                 e.vexp, s));
+                                 e.vexp, s, plan.vfold));
             std::swap(feat, feat_alt);
         } else {
             HIPCHK(launch_pw_last(packed, lay, d.f32, op, mlp, ns, d.B, d.N, d.Npad, feat, feat_out, normed,
-                                  d.f32 ? nullptr : normed_s, conf, s));
+                                  d.f32 ? nullptr : normed_s, conf, s, plan.vfold));
         }
     }
     return PDSC_OK;
@@ -526,6 +526,8 @@ int32_t pdsc_pack_weights(const pdsc_config *cfg, const float *const *P, float *
                                  has_bn ? P[wi + 5] : nullptr, in, out, f32, packed + o.w, packed + o.bias,
                                  packed + o.alpha, packed + o.beta, packed + o.scale, s);
     };
+    float *fold_tmp = nullptr;
+    HIPCHK(hipMallocAsync(reinterpret_cast<void **>(&fold_tmp), ((size_t)CH2 * CH + CH2) * sizeof(float), s));
     for (int l = 0; l < cfg->num_layers; ++l) {
         const int b = 2 + 26 * l;
         const LayerOff &lo = lay.layer[l];
@@ -536,7 +538,15 @@ int32_t pdsc_pack_weights(const pdsc_config *cfg, const float *const *P, float *
         HIPCHK(dense(lo.q, b + 20, CH, CH, false));
         HIPCHK(dense(lo.k, b + 22, CH, CH, false));
         HIPCHK(dense(lo.v, b + 24, CH, CH, false));
+        // the V fold: W0 Wv and W0 bv + b0 (fp64, rounded once) packed as a dense block
+        // of their own, with fc0's BatchNorm (launch_pack_dense takes the scale from W0 Wv)
+        // (wm, bm: a stream-ordered temporary of the call)
+        float *wm = fold_tmp, *bm = wm + (size_t)CH2 * CH;
+        HIPCHK(launch_fold_vm(P[b + 6], P[b + 7], P[b + 24], P[b + 25], wm, bm, s));
+        HIPCHK(launch_pack_dense(wm, bm, P[b + 8], P[b + 9], P[b + 10], P[b + 11], CH, CH2, f32, packed + lo.vm.w,
+                                 packed + lo.vm.bias, packed + lo.vm.alpha, packed + lo.vm.beta, packed + lo.vm.scale, s));
     }
+    HIPCHK(hipFreeAsync(fold_tmp, s));
     const int t = 2 + 26 * cfg->num_layers;
     HIPCHK(launch_copy(P[t], packed + lay.l0_w, CH * cfg->in_dim, s));
     HIPCHK(launch_copy(P[t + 1], packed + lay.l0_b, CH, s));
@@ -674,6 +684,25 @@ int32_t pdsc_encoder_plan(int32_t B, int32_t N, int32_t precision, int32_t *fuse
     if (B < 1 || N < 1 || !fused) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
     const EncoderPlan plan = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false);
     *fused = plan.fused() ? 1 : (plan.w64() ? 2 : 0);
+    return PDSC_OK;
+}
+
+int32_t pdsc_encoder_plan_vfold(int32_t B, int32_t N, int32_t precision, int32_t *vfold) {
+    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
+        return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
+    if (B < 1 || N < 1 || !vfold) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
+    *vfold = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false).vfold ? 1 : 0;
+    return PDSC_OK;
+}
+
+int32_t pdsc_packed_block(const pdsc_config *cfg, int32_t layer, int32_t block, size_t offsets[5]) {
+    RET_IF(check_cfg(cfg));
+    if (layer < 0 || layer >= cfg->num_layers || block < 0 || block > 7 || !offsets)
+        return fail(PDSC_ERR_ARG, "layer=%d block=%d", layer, block);
+    const LayerOff lo = make_layout(cfg->num_layers, cfg->in_dim).layer[layer];
+    const DenseOff d[8] = {lo.pcn, lo.fc0, lo.fc3, lo.fc6, lo.q, lo.k, lo.v, lo.vm};
+    const DenseOff &o = d[block];
+    offsets[0] = o.w, offsets[1] = o.bias, offsets[2] = o.alpha, offsets[3] = o.beta, offsets[4] = o.scale;
     return PDSC_OK;
 }
 

@@ -352,12 +352,18 @@ PDSC_DEV AttnBlock attention_h3_block(const AttnGridH3 &g, bool xcd) {
 // (wave w: the w-th of WS contiguous runs); each wave stages its own tiles into
 // a single LDS slot of its own (h3smem + w (KTB + VTB)) with no workgroup
 // barrier, and the caller merges the waves' (O, m, l) (NW must be 1).
-template <int NW, bool PACKED, bool EARLY = false, int WS = 0>
+// CV: the value width.  CH: a 128-channel V.  CH2 (EncoderPlan::vfold): the folded
+// V' in the first CV / 32 channel tiles -- the first half -- of every V tile (the
+// tile stride and the ring slots stay 16 KiB): half the V DMA, fragment reads,
+// P.V MFMAs and O registers; the loop is otherwise the same.
+template <int NW, bool PACKED, bool EARLY = false, int WS = 0, int CV = CH>
 PDSC_DEV void attention_h3_core(const _Float16 *__restrict__ Qs, const _Float16 *__restrict__ Ks,
                                 const _Float16 *__restrict__ Vs, const float *__restrict__ vexp,
                                 const float *__restrict__ M, const AttnGridH3 &g, const AttnBlock &blk, char *h3smem,
-                                int wave, int lane, f32x16 (&O)[4], float &m_run, float &l_run) {
+                                int wave, int lane, f32x16 (&O)[CV / 32], float &m_run, float &l_run) {
     static_assert(WS == 0 || (NW == 1 && !EARLY), "wave-split: one 32-query block, the plain loop");
+    static_assert(CV == CH || (CV == CH2 && WS == 0), "value width");
+    constexpr int VTB = H3_VTB * CV / CH;  // V bytes staged and read per tile
     const int b = blk.b, qb = blk.qb, split = blk.split;
     const int N = g.n(b), Npad = g.Npad;  // this pair's keys; the batch's row stride
     const int h = lane >> 5, l32 = lane & 31;
@@ -395,7 +401,8 @@ PDSC_DEV void attention_h3_core(const _Float16 *__restrict__ Qs, const _Float16 
 #endif
     auto stage = [&](int st, int slot) {
         char *dst = h3smem + (WS ? wave : slot) * (H3_KTB + H3_VTB);
-        constexpr int PIECES = (H3_KTB + H3_VTB) / 1024;
+        constexpr int PIECES = (H3_KTB + VTB) / 1024;
+        static_assert(PIECES % NW == 0, "pieces per wave");
 #pragma unroll
         for (int i = 0; i < PIECES / NW; ++i) {
             const int piece = WS ? i : wave * (PIECES / NW) + i;  // wave-uniform (SGPR)
@@ -417,7 +424,7 @@ PDSC_DEV void attention_h3_core(const _Float16 *__restrict__ Qs, const _Float16 
     };
 
 #pragma unroll
-    for (int t = 0; t < 4; ++t) O[t] = zero16();
+    for (int t = 0; t < CV / 32; ++t) O[t] = zero16();
     m_run = -INFINITY;
     l_run = 0.0f;
     const float scale = ATT_QFMA ? 1.0f : H3_QSCALE;  // (QFMA: Q carries it)
@@ -527,7 +534,7 @@ PDSC_DEV void attention_h3_core(const _Float16 *__restrict__ Qs, const _Float16 
                 m_run = m_new;
                 l_run *= alpha;
 #pragma unroll
-                for (int t = 0; t < 4; ++t)
+                for (int t = 0; t < CV / 32; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) O[t][r] *= alpha;  // lane = query
 #pragma unroll
@@ -554,7 +561,7 @@ PDSC_DEV void attention_h3_core(const _Float16 *__restrict__ Qs, const _Float16 
                 m_run = m_new;
                 l_run *= alpha;
 #pragma unroll
-                for (int t = 0; t < 4; ++t)
+                for (int t = 0; t < CV / 32; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) O[t][r] *= alpha;  // lane = query
             }
@@ -588,8 +595,8 @@ PDSC_DEV void attention_h3_core(const _Float16 *__restrict__ Qs, const _Float16 
         vread(0, vf[0]);
         vread(1, vf[1]);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (i + 2 < 8) vread(i + 2, vf[(i + 2) % 3]);
+        for (int i = 0; i < CV / 16; ++i) {
+            if (i + 2 < CV / 16) vread(i + 2, vf[(i + 2) % 3]);
             // the three products in the order of P V's mfma_h3 (pl.vh, ph.vl, ph.vh)
             f32x16 o = mfma_h(vf[i % 3][0], pl[i & 1], O[i >> 1]);
             o = mfma_h(vf[i % 3][1], ph[i & 1], o);
@@ -710,7 +717,9 @@ PDSC_DEV void attention_h3_core(const _Float16 *__restrict__ Qs, const _Float16 
     l_run = halves_sum(l_run);
 }
 
-template <int NW, bool XCD, bool PACKED, bool EARLY = false>
+// CV = CH2: the partials keep their 128-channel tiling, the first CV / 32 * 4
+// blocks of every tile -- channels 0 .. 63 -- written.
+template <int NW, bool XCD, bool PACKED, bool EARLY = false, int CV = CH>
 __global__ __launch_bounds__(NW * 64, 2) void attention_h3_kernel(
     const _Float16 *__restrict__ Qs, const _Float16 *__restrict__ Ks, const _Float16 *__restrict__ Vs,
     const float *__restrict__ vexp, const float *__restrict__ M, AttnGridH3 g, float *__restrict__ opart,
@@ -728,9 +737,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_h3_kernel(
     ATT_RSTAMP(stp, 184);
     ATT_STAMP(stp, 160);
 #endif
-    f32x16 O[4];
+    f32x16 O[CV / 32];
     float m_run, l_run;
-    attention_h3_core<NW, PACKED, EARLY>(Qs, Ks, Vs, vexp, M, g, blk, h3smem, wave, lane, O, m_run, l_run);
+    attention_h3_core<NW, PACKED, EARLY, 0, CV>(Qs, Ks, Vs, vexp, M, g, blk, h3smem, wave, lane, O, m_run, l_run);
     ATT_STAMP(stp, 161);
     ATT_RSTAMP(stp, 185);
     if (q0 >= Npad) return;
@@ -738,7 +747,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_h3_kernel(
     // registers 8u + 4g .. +3 of tile t = fragment block 2 (2t + u) + g (16 coalesced 1-KiB stores)
     float *Ob = opart + obase * CH + (size_t)(q0 >> 5) * (H3_TILE * CH) + 4 * lane;
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < CV / 32; ++t)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             *reinterpret_cast<f32x4 *>(Ob + (4 * t + q) * 256) =

@@ -32,6 +32,7 @@ struct AttnKnobs {
     bool precombine; // PDSC_PRECOMBINE=0: never
     int zigzag;      // PDSC_ZIGZAG: 0 off, 2 inverted
     bool dense_m;    // PDSC_DENSE_M=1: the forward writes and reads M dense
+    bool vfold;      // PDSC_VFOLD=0: no plan folds fc_message[0] into V (EncoderPlan::vfold)
 };
 inline const AttnKnobs &attn_knobs() {
     static const AttnKnobs k = [] {
@@ -50,6 +51,7 @@ inline const AttnKnobs &attn_knobs() {
         v.precombine = env_int("PDSC_PRECOMBINE", 1) != 0;
         v.zigzag = env_int("PDSC_ZIGZAG", 1);
         v.dense_m = env_int("PDSC_DENSE_M", 0) == 1;
+        v.vfold = env_int("PDSC_VFOLD", 1) != 0;
         return v;
     }();
     return k;
@@ -99,6 +101,13 @@ struct EncoderPlan {
     int nsplit;
     bool precombine;  // the split partials combined by combine_rows ahead of the pointwise kernels
     int m_layout;     // MLayout of the M this plan reads
+    // fc_message[0] folded into the V projection: V' = (W0 Wv) x, a
+    // 64-channel P.V, the message chain from fc0's BatchNorm / ReLU on.  True where
+    // the pointwise chain is the register-chained one (the fused plan, and the
+    // split plans from use_pw2's 320 workgroups on); attention_w64 then runs its
+    // 128-channel P.V on V' padded with zero channels.  The LDS-tiled chains (small
+    // batches) and the exact-fp32 mode keep V and fc0.
+    bool vfold;
 
     bool fused() const { return kind == ATT_FUSED; }
     bool w64() const { return kind == ATT_W64 || kind == ATT_W64_SK; }

@@ -120,6 +120,32 @@ hipError_t launch_pack_dense(const float *w, const float *b, const float *bn_w, 
     return hipGetLastError();
 }
 
+// The V fold: wm = W0 Wv [CH2][CH] and bm = W0 bv + b0 [CH2],
+// summed in fp64 (every product of two fp32 values is exact there) and rounded
+// once to fp32.  w0 [CH2][CH]: fc_message[0]; wv [CH][CH], bv: projection_v.
+__global__ void fold_vm_kernel(const float *__restrict__ w0, const float *__restrict__ b0,
+                               const float *__restrict__ wv, const float *__restrict__ bv,
+                               float *__restrict__ wm, float *__restrict__ bm) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < CH2 * CH) {
+        const int o = i / CH, c = i % CH;
+        double acc = 0.0;
+        for (int j = 0; j < CH; ++j) acc += (double)w0[o * CH + j] * (double)wv[j * CH + c];
+        wm[i] = (float)acc;
+    }
+    if (i < CH2) {
+        double acc = (double)b0[i];
+        for (int j = 0; j < CH; ++j) acc += (double)w0[i * CH + j] * (double)bv[j];
+        bm[i] = (float)acc;
+    }
+}
+
+hipError_t launch_fold_vm(const float *w0, const float *b0, const float *wv, const float *bv, float *wm, float *bm,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(fold_vm_kernel, dim3(CH2 * CH / 256), dim3(256), 0, s, w0, b0, wv, bv, wm, bm);
+    return hipGetLastError();
+}
+
 hipError_t launch_copy(const float *src, float *dst, int n, hipStream_t s) {
     hipLaunchKernelGGL(copy_kernel, dim3((n + 255) / 256), dim3(256), 0, s, src, dst, n);
     return hipGetLastError();
@@ -229,6 +255,13 @@ EncoderPlan plan_encoder(int B, int N, bool f32, bool dense_m_caller, bool allow
     // own M, and under PDSC_DENSE_M=1 on the h3 plans other than attention_w64's.
     p.m_layout = w64 || !(f32 || dense_m_caller || k.dense_m) ? M_PACKED : M_DENSE;
 
+    // The V fold goes with the kernels that have its form: the fused plan, or the
+    // register-chained chain behind attention_w64 (on zero-padded V') or behind the
+    // 4-wave h3 kernel with the in-kernel combine.  (allow_fused = false: the
+    // standalone attention, on the caller's 128-channel V.)
+    p.vfold = k.vfold && allow_fused && !f32 &&
+              (fused || (use_pw2(B, p.Npad, f32) && !p.precombine &&
+                         (p.w64() || (p.kind == ATT_H3 && p.nw == ATT_NW))));
     if (fused) {  // one key split per query block; nsplit stays the split plan's
         p.kind = ATT_FUSED;
         p.nw = PW2_W;
@@ -279,6 +312,7 @@ hipError_t launch_attention(const EncoderPlan &plan, const void *q, const void *
         break;
     }
     case ATT_H3_WS:
+        if (plan.vfold) return hipErrorInvalidValue;
         with_int<2, 4>(plan.ws, [&](auto ws) {
             with_bool(packed, [&](auto pk) {
                 constexpr int WS = decltype(ws)::value;
@@ -288,6 +322,17 @@ hipError_t launch_attention(const EncoderPlan &plan, const void *q, const void *
         });
         break;
     case ATT_H3:
+        if (plan.vfold) {  // the folded V' (the register-chained chains' plans: 4 waves)
+            if (plan.nw != ATT_NW) return hipErrorInvalidValue;
+            with_bool(plan.early, [&](auto early) {
+                with_bool(packed, [&](auto pk) {
+                    hipLaunchKernelGGL((attention_h3_kernel<ATT_NW, true, decltype(pk)::value, decltype(early)::value, CH2>),
+                                       grid, dim3(ATT_NW * 64), attention_h3_lds_bytes<ATT_NW>(), s, qs, ks, vs, vexp, M,
+                                       g, opart, ml);
+                });
+            });
+            break;
+        }
         with_int<1, 2, ATT_NW>(plan.nw, [&](auto nw) {
             with_bool(plan.early, [&](auto early) {
                 with_bool(packed, [&](auto pk) {
@@ -1469,6 +1514,44 @@ PDSC_DEV void w2_combine(const float *__restrict__ opart, const float *__restric
     }
 }
 
+// VFOLD: w2_combine over the partials' first 64 channels (blocks 0 .. 7 of a
+// tile), left as fc0's pre-activation accumulators: block 2 ks + g = registers
+// 8 (ks & 1) + 4 g .. +3 of tile ks >> 1 (as attention_h3_kernel stored them).
+PDSC_DEV void w2_combine_acc(const float *__restrict__ opart, const float *__restrict__ ml, int b, int nsplit, int Npad,
+                             int row, f32x16 (&a)[2], int lane) {
+    float mstar = -INFINITY;
+    for (int s = 0; s < nsplit; ++s) mstar = fmaxf(mstar, ml[((size_t)(b * nsplit + s) * Npad + row) * 2]);
+    float L = 0.0f;
+    f32x4 acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s = 0; s < nsplit; ++s) {
+        const size_t base = (size_t)(b * nsplit + s) * Npad + row;
+        const float ms = ml[base * 2];
+        if (ms == -INFINITY) continue;  // an empty split (w2_combine)
+        const float w = expf(ms - mstar);
+        L += w * ml[base * 2 + 1];
+        const float *src = opart + (base - (row & 31)) * CH + 4 * lane;  // the tile's first block
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] += w * *reinterpret_cast<const f32x4 *>(src + 256 * i);
+    }
+    const float rl = 1.0f / L;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[i >> 2][4 * (i & 3) + e] = acc[i][e] * rl;
+}
+
+// VFOLD: the core's 64-channel O^T -> fc0's pre-activation accumulators (O / l;
+// a one-split w2_combine_acc is exactly this)
+PDSC_DEV void w2_msg_acc(const f32x16 (&O)[2], float l_run, f32x16 (&a)[2]) {
+    const float rl = 1.0f / l_run;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a[t][r] = O[t][r] * rl;
+}
+
 // The O^T accumulators of the attention core -> the message's k-step fragments
 // (msg = O / l; registers 8u .. 8u+7 of tile t = k-step 2t + u).
 PDSC_DEV void w2_msg_frags(const f32x16 (&O)[4], float l_run, f16x8 *xh, f16x8 *xl) {
@@ -1536,13 +1619,17 @@ PDSC_DEV void w2_store_qk(const f32x16 (&acc)[4], float inv, const float *bias, 
 // <-> the key tile's v_keypos positions 16s + 8h .. +7) = fragment 2t + s of
 // this lane in the V tiling, scaled by the tile's 2^vexp (the tile's max |v| is
 // wave-local here): 16 coalesced 1-KiB stores.
-PDSC_DEV void w2_store_v(f32x16 (&acc)[4], float inv, const float *bias, _Float16 *__restrict__ Vt,
-                         float *__restrict__ vexp_t, int lane) {
+// NT = 2 (VFOLD): the folded V' = acc 2^-s (its bias went into fc0's), channel
+// tiles 0 and 1 of the V tile; pad: channel tiles 2 and 3 written as zeros
+// (attention_w64's 128-channel P.V then adds exact zeros to its upper O).
+template <int NT>
+PDSC_DEV void w2_store_v(f32x16 (&acc)[NT], float inv, const float *bias, _Float16 *__restrict__ Vt,
+                         float *__restrict__ vexp_t, int lane, bool pad = false) {
     const int h = lane >> 5, l32 = lane & 31;
     float m = 0.0f;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const float bs = bias[32 * t + l32];
+    for (int t = 0; t < NT; ++t) {
+        const float bs = NT == 4 ? bias[32 * t + l32] : 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             acc[t][r] = __builtin_fmaf(acc[t][r], inv, bs);
@@ -1551,8 +1638,16 @@ PDSC_DEV void w2_store_v(f32x16 (&acc)[4], float inv, const float *bias, _Float1
     }
     const int ev = h3_vexp(wave_max(m));
     if (lane == 0) *vexp_t = (float)ev;
+    if (NT == 2 && pad) {
+        const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
+        for (int i = 4; i < 8; ++i) {
+            *reinterpret_cast<f16x8 *>(Vt + h3_frag(i, 0, lane)) = z;
+            *reinterpret_cast<f16x8 *>(Vt + h3_frag(i, 1, lane)) = z;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             float v[8];
@@ -1570,21 +1665,24 @@ PDSC_DEV void w2_store_v(f32x16 (&acc)[4], float inv, const float *bias, _Float1
 struct W2CoefQKV {
     static constexpr int pcn = 0, q = 3 * CH, k = 4 * CH, v = 5 * CH, end = 6 * CH;
 };
-PDSC_DEV void w2_coef_qkv(float *cf, const float *pk, const PwDense4 &d, int tid) {
+// vfold: d.v is the folded block, whose V' takes no bias (its CH2 coefficients are fc0's)
+PDSC_DEV void w2_coef_qkv(float *cf, const float *pk, const PwDense4 &d, int tid, bool vfold) {
     w2_coef(cf + W2CoefQKV::pcn, pk, d.pcn, CH, tid);
     for (int i = tid; i < CH; i += PW2_W * 64) {  // Q / K / V: bias only
         cf[W2CoefQKV::q + i] = pk[d.q.bias + i];
         cf[W2CoefQKV::k + i] = pk[d.k.bias + i];
-        cf[W2CoefQKV::v + i] = pk[d.v.bias + i];
+        if (!vfold) cf[W2CoefQKV::v + i] = pk[d.v.bias + i];
     }
 }
 
 // PointCN (BN, ReLU) of the fragments x, then the Q/K/V projections; the
 // PointCN rows go to featL.  The pipeline is at the PointCN layer's first chunk.
+// VFOLD: d.v is the layer's folded block (LayerOff::vm), V' comes out 64 channels wide.
+template <bool VFOLD>
 PDSC_DEV void w2_pcn_qkv(W2Pipe &P, const float *__restrict__ pk, const W2Sched &S, const float *cf, const PwDense4 &d,
                          const f16x8 *xh, const f16x8 *xl, float *__restrict__ featL, _Float16 *__restrict__ Q,
                          _Float16 *__restrict__ K, _Float16 *__restrict__ V, float *__restrict__ vexp, int row,
-                         bool active, int wave, int lane) {
+                         bool active, int wave, int lane, bool vpad = false) {
     const int h = lane >> 5;
     f32x16 acc[4];
     f16x8 yh[8], yl[8];
@@ -1601,8 +1699,16 @@ PDSC_DEV void w2_pcn_qkv(W2Pipe &P, const float *__restrict__ pk, const W2Sched 
     w2_layer<CH, CH, true, 16>(P, pk, S, yh, yl, acc, active, wave, lane);
     if (active) w2_store_qk<false>(acc, sk, cf + W2CoefQKV::k, K, row, lane);
     CH_STAMP(177);
-    w2_layer<CH, CH, false, 16>(P, pk, S, yh, yl, acc, active, wave, lane);
-    if (active) w2_store_v(acc, sv, cf + W2CoefQKV::v, V + (size_t)(row >> 5) * H3_TILE_H, vexp + (row >> 5), lane);
+    if constexpr (VFOLD) {
+        f32x16 av[2];
+        w2_layer<CH, CH2, false, 16>(P, pk, S, yh, yl, av, active, wave, lane);
+        if (active)
+            w2_store_v<2>(av, sv, nullptr, V + (size_t)(row >> 5) * H3_TILE_H, vexp + (row >> 5), lane, vpad);
+    } else {
+        w2_layer<CH, CH, false, 16>(P, pk, S, yh, yl, acc, active, wave, lane);
+        if (active)
+            w2_store_v<4>(acc, sv, cf + W2CoefQKV::v, V + (size_t)(row >> 5) * H3_TILE_H, vexp + (row >> 5), lane);
+    }
     CH_STAMP(178);
 }
 
@@ -1611,8 +1717,9 @@ struct W2CoefMid {
     static constexpr int f0 = W2CoefQKV::end, f3 = f0 + 3 * CH2, f6 = f3 + 3 * CH2, end = f6 + 3 * CH;
 };
 static_assert(W2CoefMid::end <= PW2_COEF, "coefficient table");
-PDSC_DEV void w2_coef_mid(float *cf, const float *__restrict__ pk, const PwMsg &m, const PwDense4 &d, int tid) {
-    w2_coef_qkv(cf, pk, d, tid);
+PDSC_DEV void w2_coef_mid(float *cf, const float *__restrict__ pk, const PwMsg &m, const PwDense4 &d, int tid,
+                          bool vfold) {
+    w2_coef_qkv(cf, pk, d, tid, vfold);
     w2_coef(cf + W2CoefMid::f0, pk, m.fc0, CH2, tid);
     w2_coef(cf + W2CoefMid::f3, pk, m.fc3, CH2, tid);
     w2_coef(cf + W2CoefMid::f6, pk, m.fc6, CH, tid);
@@ -1620,16 +1727,25 @@ PDSC_DEV void w2_coef_mid(float *cf, const float *__restrict__ pk, const PwMsg &
 
 // fc_message + residual + PointCN + QKV from the message fragments x (after the
 // combine); the pipeline is at fc0's first chunk.  featL, Q, K, V, vexp: the pair's.
+// VFOLD: a2 holds the folded message (fc0's pre-activation without its bias;
+// w2_msg_acc / w2_combine_acc), m.fc0 is the layer's folded block, whose
+// coefficients are W0 bv + b0 and fc0's BatchNorm, and the pipeline is at fc3's
+// first chunk; x is then scratch.
+template <bool VFOLD>
 PDSC_DEV void w2_mid_chain(W2Pipe &P, const float *__restrict__ pk, const W2Sched &S, const float *cf, const PwMsg &m,
-                           const PwDense4 &d, f16x8 *xh, f16x8 *xl, const float *featL_in, float *featL,
+                           const PwDense4 &d, f16x8 *xh, f16x8 *xl, f32x16 (&a2)[2], const float *featL_in, float *featL,
                            _Float16 *__restrict__ Q, _Float16 *__restrict__ K, _Float16 *__restrict__ V,
-                           float *__restrict__ vexp, int row, bool active, int wave, int lane) {
+                           float *__restrict__ vexp, int row, bool active, int wave, int lane, bool vpad = false) {
     // featL_in: the residual rows; featL: where the PointCN rows go (each lane
     // reads and writes only its own row, so the two may be one buffer)
-    f32x16 a2[2], a4[4], res[4];
+    f32x16 a4[4], res[4];
     f16x8 yh[8], yl[8];
-    w2_layer<CH, CH2, true>(P, pk, S, xh, xl, a2, active, wave, lane);
-    if (active) w2_epilogue<CH2, EPI_BN_RELU>(a2, pk[m.fc0.scale], cf + W2CoefMid::f0, nullptr, yh, yl, lane);
+    if constexpr (VFOLD) {
+        if (active) w2_epilogue<CH2, EPI_BN_RELU>(a2, 1.0f, cf + W2CoefMid::f0, nullptr, yh, yl, lane);
+    } else {
+        w2_layer<CH, CH2, true>(P, pk, S, xh, xl, a2, active, wave, lane);
+        if (active) w2_epilogue<CH2, EPI_BN_RELU>(a2, pk[m.fc0.scale], cf + W2CoefMid::f0, nullptr, yh, yl, lane);
+    }
     CH_STAMP(172);
     w2_layer<CH2, CH2, true>(P, pk, S, yh, yl, a2, active, wave, lane);
     if (active) {
@@ -1640,7 +1756,7 @@ PDSC_DEV void w2_mid_chain(W2Pipe &P, const float *__restrict__ pk, const W2Sche
     w2_layer<CH2, CH, true, 16>(P, pk, S, xh, xl, a4, active, wave, lane);
     if (active) w2_epilogue<CH, EPI_RESID>(a4, pk[m.fc6.scale], cf + W2CoefMid::f6, res, yh, yl, lane);
     CH_STAMP(174);
-    w2_pcn_qkv(P, pk, S, cf, d, yh, yl, featL, Q, K, V, vexp, row, active, wave, lane);
+    w2_pcn_qkv<VFOLD>(P, pk, S, cf, d, yh, yl, featL, Q, K, V, vexp, row, active, wave, lane, vpad);
 }
 
 #define PW2_PROLOGUE                                                                              \
@@ -1655,12 +1771,13 @@ PDSC_DEV void w2_mid_chain(W2Pipe &P, const float *__restrict__ pk, const W2Sche
 
 // layer0 (Conv1d in_dim -> 128 on exact fp32 MFMA 32x32x2, k-step j: inputs 2j + h)
 // + PointCN_0 + QKV_0.
+template <bool VFOLD>
 __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void pw2_first_kernel(const float *__restrict__ pk, W2Sched S, size_t l0w,
                                                                  size_t l0b, PwDense4 d, const float *__restrict__ corr,
                                                                  int in_dim, int N, int Npad, float *__restrict__ featL,
                                                                  _Float16 *__restrict__ Q, _Float16 *__restrict__ K,
                                                                  _Float16 *__restrict__ V, float *__restrict__ vexp,
-                                                                 const int *__restrict__ nv) {
+                                                                 const int *__restrict__ nv, int vpad) {
     // ragged batches: a workgroup wholly past its pair's rows has nothing any later
     // kernel reads (the attention's key tiles end at round_up(n, 32) <= its first
     // row; its query blocks past n exit) -- leave before staging any weights
@@ -1668,7 +1785,7 @@ __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void pw2_first_kernel(const fl
     PW2_PROLOGUE
     const int l32 = lane & 31;
     const int n = nv ? nv[b] : N;  // this pair's rows (ragged batches); N: the row stride
-    w2_coef_qkv(cf, pk, d, tid);
+    w2_coef_qkv(cf, pk, d, tid, VFOLD);
     f16x8 xh[8], xl[8];
     if (active) {
         const float *cp = corr + ((size_t)b * N + min(row, n - 1)) * in_dim;
@@ -1694,11 +1811,13 @@ __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void pw2_first_kernel(const fl
             }
     }
     __syncthreads();
-    w2_pcn_qkv(P, pk, S, cf, d, xh, xl, featL + boff, Q + 2 * boff, K + 2 * boff, V + 2 * boff,
-               vexp + (size_t)b * (Npad / 32), row, active, wave, lane);
+    w2_pcn_qkv<VFOLD>(P, pk, S, cf, d, xh, xl, featL + boff, Q + 2 * boff, K + 2 * boff, V + 2 * boff,
+                      vexp + (size_t)b * (Npad / 32), row, active, wave, lane, vpad != 0);
 }
 
 // combine_l + fc_message_l + residual + PointCN_{l+1} + QKV_{l+1}.
+// VFOLD: V' padded with zero channels (the attention may be attention_w64's).
+template <bool VFOLD>
 __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void pw2_mid_kernel(const float *__restrict__ pk, W2Sched S, PwMsg m,
                                                                PwDense4 d, const float *__restrict__ opart,
                                                                const float *__restrict__ ml, int nsplit, int N,
@@ -1707,12 +1826,18 @@ __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void pw2_mid_kernel(const floa
                                                                _Float16 *__restrict__ Q, _Float16 *__restrict__ K,
                                                                _Float16 *__restrict__ V, float *__restrict__ vexp) {
     PW2_PROLOGUE
-    w2_coef_mid(cf, pk, m, d, tid);
+    w2_coef_mid(cf, pk, m, d, tid, VFOLD);
     f16x8 xh[8], xl[8];
-    if (active) w2_combine(opart, ml, b, nsplit, Npad, row, xh, xl, lane);
+    f32x16 a2[2];
+    if (active) {
+        if constexpr (VFOLD)
+            w2_combine_acc(opart, ml, b, nsplit, Npad, row, a2, lane);
+        else
+            w2_combine(opart, ml, b, nsplit, Npad, row, xh, xl, lane);
+    }
     __syncthreads();
-    w2_mid_chain(P, pk, S, cf, m, d, xh, xl, featL_in + boff, featL + boff, Q + 2 * boff, K + 2 * boff,
-                 V + 2 * boff, vexp + (size_t)b * (Npad / 32), row, active, wave, lane);
+    w2_mid_chain<VFOLD>(P, pk, S, cf, m, d, xh, xl, a2, featL_in + boff, featL + boff, Q + 2 * boff, K + 2 * boff,
+                        V + 2 * boff, vexp + (size_t)b * (Npad / 32), row, active, wave, lane, true);
 }
 
 // attention_l + fc_message_l + residual + PointCN_{l+1} + QKV_{l+1} in ONE
@@ -1724,7 +1849,7 @@ __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void pw2_mid_kernel(const floa
 // buffers (Q, K, V, vexp): other workgroups of the pair still read layer l.
 // Bit-identical to attention_h3_kernel + pw2_mid_kernel (a one-split combine
 // is O * (1 / l) exactly).  LDS: the K/V ring, then the weight ring.
-template <bool PACKED>
+template <bool PACKED, bool VFOLD>
 __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void attn_pw2_kernel(
     const _Float16 *__restrict__ Qs, const _Float16 *__restrict__ Ks, const _Float16 *__restrict__ Vs,
     const float *__restrict__ vexp_in, const float *__restrict__ M, AttnGridH3 g, const float *__restrict__ pk,
@@ -1743,21 +1868,29 @@ __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void attn_pw2_kernel(
     ATT_RSTAMP(stp, 188);
     ATT_STAMP(stp, 0);
 #endif
-    f32x16 O[4];
+    constexpr int CV = VFOLD ? CH2 : CH;
+    f32x16 O[CV / 32];
     float m_run, l_run;
-    attention_h3_core<PW2_W, PACKED, PW2_EARLY>(Qs, Ks, Vs, vexp_in, M, g, blk, w2smem, wave, lane, O, m_run, l_run);
+    attention_h3_core<PW2_W, PACKED, PW2_EARLY, 0, CV>(Qs, Ks, Vs, vexp_in, M, g, blk, w2smem, wave, lane, O, m_run,
+                                                       l_run);
     ATT_STAMP(stp, 170);
     // the K/V ring is free (the core ends on a barrier): weight chunks 0, 1 and the coefficients
     W2Pipe P{w2smem, 0};
     float *cf = reinterpret_cast<float *>(w2smem + PW2_NSLOT * PW2_SLOT);
     for (int c = 0; c < PW2_NSLOT; ++c) w2_stage(pk, S, c, P.slot(c), wave, lane);
-    w2_coef_mid(cf, pk, m, d, tid);
+    w2_coef_mid(cf, pk, m, d, tid, VFOLD);
     f16x8 xh[8], xl[8];
-    if (active) w2_msg_frags(O, l_run, xh, xl);  // msg = O / l
+    f32x16 a2[2];
+    if (active) {  // msg = O / l
+        if constexpr (VFOLD)
+            w2_msg_acc(O, l_run, a2);
+        else
+            w2_msg_frags(O, l_run, xh, xl);
+    }
     __syncthreads();
     ATT_STAMP(stp, 171);
-    w2_mid_chain(P, pk, S, cf, m, d, xh, xl, featL + boff, featL + boff, Q + 2 * boff, K + 2 * boff,
-                 V + 2 * boff, vexp + (size_t)b * (Npad / 32), row, active, wave, lane);
+    w2_mid_chain<VFOLD>(P, pk, S, cf, m, d, xh, xl, a2, featL + boff, featL + boff, Q + 2 * boff, K + 2 * boff,
+                        V + 2 * boff, vexp + (size_t)b * (Npad / 32), row, active, wave, lane);
     ATT_STAMP(stp, 180);
     ATT_RSTAMP(stp, 189);
 }
@@ -1792,18 +1925,24 @@ PDSC_DEV void w2_coef_last(float *cf, const float *__restrict__ pk, const PwMsg 
 
 // fc_message + residual from the message fragments x, then F.normalize (:156)
 // and the classifier (:171); the pipeline is at fc0's first chunk.  featL: the pair's.
+// VFOLD: as w2_mid_chain's.
+template <bool VFOLD>
 PDSC_DEV void w2_last_chain(W2Pipe &P, const float *__restrict__ pk, const W2Sched &S, const float *cf, const PwMsg &m,
-                            const DenseOff &c0, const DenseOff &c2, size_t c4b, f16x8 *xh, f16x8 *xl,
+                            const DenseOff &c0, const DenseOff &c2, size_t c4b, f16x8 *xh, f16x8 *xl, f32x16 (&a2)[2],
                             const float *__restrict__ featL, float *__restrict__ feat_out, float *__restrict__ normed,
                             _Float16 *__restrict__ normed_s, float *__restrict__ conf, int b, int N, int row,
                             bool active, int wave, int lane) {
     constexpr int CF0 = W2CoefLast::f0, CF3 = W2CoefLast::f3, CF6 = W2CoefLast::f6, CC0 = W2CoefLast::c0,
                   CC2 = W2CoefLast::c2, CC4 = W2CoefLast::c4;
     const int h = lane >> 5;
-    f32x16 a1[1], a2[2], a4[4], res[4];
+    f32x16 a1[1], a4[4], res[4];
     f16x8 yh[8], yl[8];
-    w2_layer<CH, CH2, true>(P, pk, S, xh, xl, a2, active, wave, lane);
-    if (active) w2_epilogue<CH2, EPI_BN_RELU>(a2, pk[m.fc0.scale], cf + CF0, nullptr, yh, yl, lane);
+    if constexpr (VFOLD) {
+        if (active) w2_epilogue<CH2, EPI_BN_RELU>(a2, 1.0f, cf + CF0, nullptr, yh, yl, lane);
+    } else {
+        w2_layer<CH, CH2, true>(P, pk, S, xh, xl, a2, active, wave, lane);
+        if (active) w2_epilogue<CH2, EPI_BN_RELU>(a2, pk[m.fc0.scale], cf + CF0, nullptr, yh, yl, lane);
+    }
     w2_layer<CH2, CH2, true>(P, pk, S, yh, yl, a2, active, wave, lane);
     if (active) {
         w2_epilogue<CH2, EPI_BN_RELU>(a2, pk[m.fc3.scale], cf + CF3, nullptr, xh, xl, lane);
@@ -1868,6 +2007,7 @@ PDSC_DEV void w2_last_chain(W2Pipe &P, const float *__restrict__ pk, const W2Sch
 }
 
 // combine + fc_message + residual, then F.normalize (:156) and the classifier (:171).
+template <bool VFOLD>
 __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void pw2_last_kernel(
     const float *__restrict__ pk, W2Sched S, PwMsg m, DenseOff c0, DenseOff c2, size_t c4w, size_t c4b,
     const float *__restrict__ opart, const float *__restrict__ ml, int nsplit, int N, int Npad,
@@ -1876,16 +2016,22 @@ __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void pw2_last_kernel(
     PW2_PROLOGUE
     w2_coef_last(cf, pk, m, c0, c2, c4w, tid);
     f16x8 xh[8], xl[8];
-    if (active) w2_combine(opart, ml, b, nsplit, Npad, row, xh, xl, lane);
+    f32x16 a2[2];
+    if (active) {
+        if constexpr (VFOLD)
+            w2_combine_acc(opart, ml, b, nsplit, Npad, row, a2, lane);
+        else
+            w2_combine(opart, ml, b, nsplit, Npad, row, xh, xl, lane);
+    }
     __syncthreads();
-    w2_last_chain(P, pk, S, cf, m, c0, c2, c4b, xh, xl, featL + boff, feat_out, normed, normed_s, conf, b, N, row,
-                  active, wave, lane);
+    w2_last_chain<VFOLD>(P, pk, S, cf, m, c0, c2, c4b, xh, xl, a2, featL + boff, feat_out, normed, normed_s, conf, b, N,
+                         row, active, wave, lane);
 }
 
 // attention_{L-1} + fc_message_{L-1} + residual + normalize + classifier in ONE
 // launch (as attn_pw2_kernel for the last layer): bit-identical to
 // attention_h3_kernel + pw2_last_kernel with one key split.
-template <bool PACKED>
+template <bool PACKED, bool VFOLD>
 __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void attn_pw2_last_kernel(
     const _Float16 *__restrict__ Qs, const _Float16 *__restrict__ Ks, const _Float16 *__restrict__ Vs,
     const float *__restrict__ vexp_in, const float *__restrict__ M, AttnGridH3 g, const float *__restrict__ pk,
@@ -1899,38 +2045,48 @@ __global__ __launch_bounds__(PW2_W * 64, PW2_OCC) void attn_pw2_last_kernel(
               lane = tid & 63;
     const int row = blk.qb * PW2_PTS + wave * 32 + (lane & 31);
     const bool active = blk.qb * PW2_PTS + wave * 32 < Npad;  // wave-uniform
-    f32x16 O[4];
+    constexpr int CV = VFOLD ? CH2 : CH;
+    f32x16 O[CV / 32];
     float m_run, l_run;
-    attention_h3_core<PW2_W, PACKED, PW2_EARLY>(Qs, Ks, Vs, vexp_in, M, g, blk, w2smem, wave, lane, O, m_run, l_run);
+    attention_h3_core<PW2_W, PACKED, PW2_EARLY, 0, CV>(Qs, Ks, Vs, vexp_in, M, g, blk, w2smem, wave, lane, O, m_run,
+                                                       l_run);
     W2Pipe P{w2smem, 0};
     float *cf = reinterpret_cast<float *>(w2smem + PW2_NSLOT * PW2_SLOT);
     for (int c = 0; c < PW2_NSLOT; ++c) w2_stage(pk, S, c, P.slot(c), wave, lane);
     w2_coef_last(cf, pk, m, c0, c2, c4w, tid);
     f16x8 xh[8], xl[8];
-    if (active) w2_msg_frags(O, l_run, xh, xl);
+    f32x16 a2[2];
+    if (active) {
+        if constexpr (VFOLD)
+            w2_msg_acc(O, l_run, a2);
+        else
+            w2_msg_frags(O, l_run, xh, xl);
+    }
     __syncthreads();
-    w2_last_chain(P, pk, S, cf, m, c0, c2, c4b, xh, xl, featL + (size_t)b * Npad * CH, feat_out, normed, normed_s,
-                  conf, b, N, row, active, wave, lane);
+    w2_last_chain<VFOLD>(P, pk, S, cf, m, c0, c2, c4b, xh, xl, a2, featL + (size_t)b * Npad * CH, feat_out, normed,
+                         normed_s, conf, b, N, row, active, wave, lane);
 }
 #undef PW2_PROLOGUE
 
-static W2Sched sched_qkv(W2Sched S, const PwDense4 &d) {
+// vfold: d.v and m.fc0 are the layer's folded block (dense4 / msg3): V' is 128 -> 64,
+// and fc0's product is gone from the message chain.
+static W2Sched sched_qkv(W2Sched S, const PwDense4 &d, bool vfold) {
     w2_sched_add(S, d.pcn, CH, CH);
     w2_sched_add(S, d.q, CH, CH);
     w2_sched_add(S, d.k, CH, CH);
-    w2_sched_add(S, d.v, CH, CH);
+    w2_sched_add(S, d.v, CH, vfold ? CH2 : CH);
     return S;
 }
-static W2Sched sched_msg(const PwMsg &m) {
+static W2Sched sched_msg(const PwMsg &m, bool vfold) {
     W2Sched S{};
-    w2_sched_add(S, m.fc0, CH, CH2);
+    if (!vfold) w2_sched_add(S, m.fc0, CH, CH2);
     w2_sched_add(S, m.fc3, CH2, CH2);
     w2_sched_add(S, m.fc6, CH2, CH);
     return S;
 }
 
-static PwDense4 dense4(const LayerOff &l) { return PwDense4{l.pcn, l.q, l.k, l.v}; }
-static PwMsg msg3(const LayerOff &l) { return PwMsg{l.fc0, l.fc3, l.fc6}; }
+static PwDense4 dense4(const LayerOff &l, bool vfold = false) { return PwDense4{l.pcn, l.q, l.k, vfold ? l.vm : l.v}; }
+static PwMsg msg3(const LayerOff &l, bool vfold = false) { return PwMsg{vfold ? l.vm : l.fc0, l.fc3, l.fc6}; }
 
 // The fused launches (the plan's ATT_FUSED): one key split per query block, a
 // workgroup per PW2_PTS queries.
@@ -1939,15 +2095,20 @@ hipError_t launch_attn_pw2(const EncoderPlan &plan, const float *packed, const P
                            float *feat, void *qo, void *ko, void *vo, float *vexp_out, hipStream_t s, Ragged rg) {
     if (!plan.fused() || layer + 1 >= lay.L) return hipErrorInvalidValue;
     const AttnGridH3 g = plan_grid_h3(plan, rg, layer);
-    const W2Sched S = sched_qkv(sched_msg(msg3(lay.layer[layer])), dense4(lay.layer[layer + 1]));
+    const bool vf = plan.vfold;
+    const PwMsg m = msg3(lay.layer[layer], vf);
+    const PwDense4 d = dense4(lay.layer[layer + 1], vf);
+    const W2Sched S = sched_qkv(sched_msg(m, vf), d, vf);
     const size_t lds = std::max(attention_h3_lds_bytes<PW2_W>(), PW2_LDS);
     const _Float16 *qs = static_cast<const _Float16 *>(q), *ks = static_cast<const _Float16 *>(k),
                    *vs = static_cast<const _Float16 *>(v);
     _Float16 *Q = static_cast<_Float16 *>(qo), *K = static_cast<_Float16 *>(ko), *V = static_cast<_Float16 *>(vo);
     with_bool(plan.m_layout == M_PACKED, [&](auto pk) {
-        hipLaunchKernelGGL(attn_pw2_kernel<decltype(pk)::value>, dim3(plan.workgroups()), dim3(PW2_W * 64), lds, s, qs,
-                           ks, vs, vexp_in, M, g, packed, S, msg3(lay.layer[layer]), dense4(lay.layer[layer + 1]), feat,
-                           Q, K, V, vexp_out);
+        with_bool(vf, [&](auto vfold) {
+            hipLaunchKernelGGL((attn_pw2_kernel<decltype(pk)::value, decltype(vfold)::value>), dim3(plan.workgroups()),
+                               dim3(PW2_W * 64), lds, s, qs, ks, vs, vexp_in, M, g, packed, S, m, d, feat, Q, K, V,
+                               vexp_out);
+        });
     });
     return hipGetLastError();
 }
@@ -1958,17 +2119,20 @@ hipError_t launch_attn_pw2_last(const EncoderPlan &plan, const float *packed, co
                                 Ragged rg) {
     if (!plan.fused()) return hipErrorInvalidValue;
     const AttnGridH3 g = plan_grid_h3(plan, rg, lay.L - 1);
-    W2Sched S = sched_msg(msg3(lay.layer[lay.L - 1]));
+    const bool vf = plan.vfold;
+    const PwMsg m = msg3(lay.layer[lay.L - 1], vf);
+    W2Sched S = sched_msg(m, vf);
     w2_sched_add(S, lay.c0, CH, CLS);
     w2_sched_add(S, lay.c2, CLS, CLS);
     const size_t lds = std::max(attention_h3_lds_bytes<PW2_W>(), PW2_LDS);
     const _Float16 *qs = static_cast<const _Float16 *>(q), *ks = static_cast<const _Float16 *>(k),
                    *vs = static_cast<const _Float16 *>(v);
-    const PwMsg m = msg3(lay.layer[lay.L - 1]);
     with_bool(plan.m_layout == M_PACKED, [&](auto pk) {
-        hipLaunchKernelGGL(attn_pw2_last_kernel<decltype(pk)::value>, dim3(plan.workgroups()), dim3(PW2_W * 64), lds, s,
-                           qs, ks, vs, vexp_in, M, g, packed, S, m, lay.c0, lay.c2, lay.c4_w, lay.c4_b, feat, feat_out,
-                           normed, normed_s, conf);
+        with_bool(vf, [&](auto vfold) {
+            hipLaunchKernelGGL((attn_pw2_last_kernel<decltype(pk)::value, decltype(vfold)::value>),
+                               dim3(plan.workgroups()), dim3(PW2_W * 64), lds, s, qs, ks, vs, vexp_in, M, g, packed, S, m,
+                               lay.c0, lay.c2, lay.c4_w, lay.c4_b, feat, feat_out, normed, normed_s, conf);
+        });
     });
     return hipGetLastError();
 }
@@ -2024,16 +2188,20 @@ static bool pw_qkv_split(int B, int Npad) {
 
 hipError_t launch_pw_first(const float *packed, const PackLayout &lay, const float *corr_pos, bool f32, int B,
                            int N, int Npad, float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s,
-                           Ragged rg, bool fused) {
+                           Ragged rg, bool fused, bool vfold) {
     if (lay.in_dim > IN_LIMIT) return hipErrorInvalidValue;
     _Float16 *Q = static_cast<_Float16 *>(q), *K = static_cast<_Float16 *>(k), *V = static_cast<_Float16 *>(v);
     if (fused || use_pw2(B, Npad, f32)) {  // the fused plan's layouts (a part of a batch: the batch's plan)
-        const W2Sched S = sched_qkv(W2Sched{}, dense4(lay.layer[0]));
-        hipLaunchKernelGGL(pw2_first_kernel, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B), dim3(PW2_W * 64), PW2_LDS, s,
-                           packed, S, lay.l0_w, lay.l0_b, dense4(lay.layer[0]), corr_pos, lay.in_dim, N, Npad, feat, Q, K,
-                           V, vexp, rg.nv);
+        const PwDense4 d = dense4(lay.layer[0], vfold);
+        const W2Sched S = sched_qkv(W2Sched{}, d, vfold);
+        with_bool(vfold, [&](auto vf) {
+            hipLaunchKernelGGL(pw2_first_kernel<decltype(vf)::value>, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B),
+                               dim3(PW2_W * 64), PW2_LDS, s, packed, S, lay.l0_w, lay.l0_b, d, corr_pos, lay.in_dim, N,
+                               Npad, feat, Q, K, V, vexp, rg.nv, (int)!fused);
+        });
         return hipGetLastError();
     }
+    if (vfold) return hipErrorInvalidValue;  // the register-chained kernels only
     if (!f32 && small_tiles(B, Npad) && pw_qkv_split(B, Npad)) {  // Q / K / V in three workgroups per tile
         hipLaunchKernelGGL((pw_first_kernel<32, false>), dim3(Npad / 32, B, 3), dim3(256), pw_lds<32>(), s, packed,
                            lay.l0_w, lay.l0_b, dense4(lay.layer[0]), corr_pos, lay.in_dim, N, Npad, feat, Q, K, V, vexp,
@@ -2047,16 +2215,21 @@ hipError_t launch_pw_first(const float *packed, const PackLayout &lay, const flo
 
 hipError_t launch_pw_mid(const float *packed, const PackLayout &lay, int layer, bool f32, const float *opart,
                          const float *ml, int nsplit, int B, int N, int Npad, const float *feat_in, float *feat,
-                         void *q, void *k, void *v, float *vexp, hipStream_t s) {
+                         void *q, void *k, void *v, float *vexp, hipStream_t s, bool vfold) {
     const int delay = g_diag_qkv_delay;  // tests only (pdsc_diag_qkv_delay): delay the split's K / V workgroups
     _Float16 *Q = static_cast<_Float16 *>(q), *K = static_cast<_Float16 *>(k), *V = static_cast<_Float16 *>(v);
     if (use_pw2(B, Npad, f32)) {
-        const W2Sched S = sched_qkv(sched_msg(msg3(lay.layer[layer])), dense4(lay.layer[layer + 1]));
-        hipLaunchKernelGGL(pw2_mid_kernel, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B), dim3(PW2_W * 64), PW2_LDS, s,
-                           packed, S, msg3(lay.layer[layer]), dense4(lay.layer[layer + 1]), opart, ml, nsplit, N, Npad,
-                           feat_in, feat, Q, K, V, vexp);
+        const PwMsg m = msg3(lay.layer[layer], vfold);
+        const PwDense4 d = dense4(lay.layer[layer + 1], vfold);
+        const W2Sched S = sched_qkv(sched_msg(m, vfold), d, vfold);
+        with_bool(vfold, [&](auto vf) {
+            hipLaunchKernelGGL(pw2_mid_kernel<decltype(vf)::value>, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B),
+                               dim3(PW2_W * 64), PW2_LDS, s, packed, S, m, d, opart, ml, nsplit, N, Npad, feat_in, feat, Q,
+                               K, V, vexp);
+        });
         return hipGetLastError();
     }
+    if (vfold) return hipErrorInvalidValue;  // the register-chained kernels only
     if (!f32 && pw_waves8(B, Npad)) {
         hipLaunchKernelGGL((pw_mid_kernel<32, false, 8>), dim3(Npad / 32, B, pw_qkv_split(B, Npad) ? 3 : 1), dim3(512),
                            pw_lds<32>(), s, packed,
@@ -2071,16 +2244,21 @@ hipError_t launch_pw_mid(const float *packed, const PackLayout &lay, int layer, 
 
 hipError_t launch_pw_last(const float *packed, const PackLayout &lay, bool f32, const float *opart,
                           const float *ml, int nsplit, int B, int N, int Npad, const float *feat,
-                          float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s) {
+                          float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
+                          bool vfold) {
     if (use_pw2(B, Npad, f32)) {
-        W2Sched S = sched_msg(msg3(lay.layer[lay.L - 1]));
+        const PwMsg m = msg3(lay.layer[lay.L - 1], vfold);
+        W2Sched S = sched_msg(m, vfold);
         w2_sched_add(S, lay.c0, CH, CLS);
         w2_sched_add(S, lay.c2, CLS, CLS);
-        hipLaunchKernelGGL(pw2_last_kernel, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B), dim3(PW2_W * 64), PW2_LDS, s,
-                           packed, S, msg3(lay.layer[lay.L - 1]), lay.c0, lay.c2, lay.c4_w, lay.c4_b, opart, ml, nsplit, N,
-                           Npad, feat, feat_out, normed, normed_s, conf);
+        with_bool(vfold, [&](auto vf) {
+            hipLaunchKernelGGL(pw2_last_kernel<decltype(vf)::value>, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B),
+                               dim3(PW2_W * 64), PW2_LDS, s, packed, S, m, lay.c0, lay.c2, lay.c4_w, lay.c4_b, opart, ml,
+                               nsplit, N, Npad, feat, feat_out, normed, normed_s, conf);
+        });
         return hipGetLastError();
     }
+    if (vfold) return hipErrorInvalidValue;  // the register-chained kernels only
     PW_LAUNCH(pw_last_kernel, N, packed, msg3(lay.layer[lay.L - 1]), lay.c0, lay.c2, lay.c4_w, lay.c4_b, opart, ml,
               nsplit, N, Npad, feat, feat_out, normed, normed_s, conf);
     return hipGetLastError();

@@ -68,8 +68,12 @@ struct DenseOff {
     size_t w, bias, alpha, beta, scale;
 };
 
+// vm: the V fold: W0 Wv [CH2][CH] as a dense block with bias
+// W0 bv + b0 and fc0's BatchNorm alpha / beta -- the plans with
+// EncoderPlan::vfold project V through it and start the message chain at
+// fc0's epilogue; the other plans read v and fc0.
 struct LayerOff {
-    DenseOff pcn, fc0, fc3, fc6, q, k, v;
+    DenseOff pcn, fc0, fc3, fc6, q, k, v, vm;
 };
 
 struct PackLayout {
@@ -128,6 +132,8 @@ inline PackLayout make_layout(int L, int in_dim) {
     o += CLS;
     p.c4_b = o;
     o += 4;
+    // appended, so that no earlier offset moves: the folded blocks
+    for (int l = 0; l < L; ++l) p.layer[l].vm = dense_at(o, CH, CH2);
     p.total = o;
     return p;
 }
@@ -169,6 +175,9 @@ hipError_t launch_pack_dense(const float *w, const float *b, const float *bn_w, 
                              const float *bn_rm, const float *bn_rv, int in, int out, bool f32, float *dst_w,
                              float *dst_b, float *dst_a, float *dst_beta, float *dst_scale, hipStream_t s);
 hipError_t launch_copy(const float *src, float *dst, int n, hipStream_t s);
+// The V fold's weights in fp64, each rounded once to fp32: wm [CH2][CH] = W0 Wv, bm [CH2] = W0 bv + b0.
+hipError_t launch_fold_vm(const float *w0, const float *b0, const float *wv, const float *bv, float *wm, float *bm,
+                          hipStream_t s);
 
 // Attention partials for one layer: opart [B][nsplit][Npad x CH], ml [B][nsplit][Npad][2];
 // opart rows [Npad][CH] for f32, the fragment-block tiling of attention_h3.hpp
@@ -206,10 +215,14 @@ hipError_t launch_attn_combine(const float *opart, const float *ml, bool f32, in
                                int nsplit, float *msg, hipStream_t s);
 
 // Pointwise chains (one workgroup per PT points); q, k, v in launch_attention's layouts.
+// vfold (EncoderPlan::vfold; the register-chained kernels only): V is the folded
+// 64-channel V' in the first half of every V tile (the second half zero unless
+// fused, for attention_w64's 128-channel P.V), the partials' first 64 channels
+// are the folded O, and the message chain starts at fc0's BatchNorm / ReLU.
 // fused: the batch runs the fused plan (EncoderPlan::fused), whatever B this call covers.
 hipError_t launch_pw_first(const float *packed, const PackLayout &lay, const float *corr_pos, bool f32, int B,
                            int N, int Npad, float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s,
-                           Ragged rg = {}, bool fused = false);
+                           Ragged rg = {}, bool fused = false, bool vfold = false);
 // H3 split partials (nsplit) -> one combined split (opart1 [B][Npad][CH] in the
 // h3 tiling, ml1 = (0, 1)) that pw_mid / pw_last read with nsplit = 1 (small
 // batches: combine16's per-thread load chain is the pointwise launch's latency).
@@ -220,10 +233,11 @@ hipError_t launch_combine_rows(const float *opart, const float *ml, int B, int N
 // feat_in while one of them writes feat)
 hipError_t launch_pw_mid(const float *packed, const PackLayout &lay, int layer, bool f32, const float *opart,
                          const float *ml, int nsplit, int B, int N, int Npad, const float *feat_in, float *feat,
-                         void *q, void *k, void *v, float *vexp, hipStream_t s);
+                         void *q, void *k, void *v, float *vexp, hipStream_t s, bool vfold = false);
 hipError_t launch_pw_last(const float *packed, const PackLayout &lay, bool f32, const float *opart,
                           const float *ml, int nsplit, int B, int N, int Npad, const float *feat,
-                          float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s);
+                          float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
+                          bool vfold = false);
 
 hipError_t launch_local_max(const float *src, const float *conf, int B, int N, float radius,
                             float *lm, hipStream_t s, Ragged rg = {});
