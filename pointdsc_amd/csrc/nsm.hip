@@ -1026,8 +1026,9 @@ __global__ __launch_bounds__(256, 4) void nsm_seed_kernel(const void *__restrict
     __builtin_amdgcn_wave_barrier();  // P and the Gram triangle visible to the wave
     const int npair = k * (k - 1) / 2;
     // the pair table entry of the next pass is loaded one pass ahead (a global
-    // load per pass otherwise exposes its whole latency, 13 passes at k = 40)
-    unsigned pc_next = g_nsm_pairs.v[min(lane, npair - 1)];
+    // load per pass otherwise exposes its whole latency, 13 passes at k = 40);
+    // k = 1 has no pair: the prefetch still reads inside the table
+    unsigned pc_next = g_nsm_pairs.v[max(min(lane, npair - 1), 0)];
     for (int p = lane; p < npair; p += 64) {
         const unsigned pc = pc_next;
         pc_next = g_nsm_pairs.v[min(p + 64, npair - 1)];
