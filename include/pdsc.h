@@ -391,6 +391,44 @@ int32_t pdsc_compute_fpfh(const float *pts, const float *normals, int32_t n, flo
                           double *fpfh, float *fpfh_normalized, void *workspace, size_t workspace_bytes,
                           pdsc_stream_t stream);
 
+/* ------------------------------------------- f5 ICP refinement -------------
+ * The "+ICP" stage of the reference's drivers: o3d registration_icp(src, tgt,
+ * max_distance, init, TransformationEstimationPointToPoint()) seeded with the
+ * forward's final_trans (test.py:183-189, distance 0.6; evaluation/
+ * benchmark_utils.py:40-56 icp_refine, distance 0.1, used by test.py,
+ * multiway/test_multi.py:53-54 and multiway/test_multi_ate.py).  open3d's
+ * RegistrationICP with its default criteria restated (parity with open3d
+ * itself is unpinned): T maps source to target (T [x;1]); evaluate(T) pairs
+ * every source point q = R p + t (fp64) with its nearest target point within
+ * d^2 <= max_distance^2 (fp64 d^2, pdsc_radius_knn's inclusion, ties to the
+ * lower target index), fitness = n_corr / Ns, inlier_rmse = sqrt(sum d^2 /
+ * n_corr) (0 without correspondences).  Starting from evaluate(init), at most
+ * max_iteration times: T <- Kabsch(correspondences) T (unit weights, fp64,
+ * identity without correspondences), evaluate(T), and stop once |fitness
+ * change| < relative_fitness and |rmse change| < relative_rmse (open3d's
+ * defaults: 30, 1e-6, 1e-6).  max_iteration = 0 only evaluates init.  T and
+ * every sum stay fp64 on the device, summed in a fixed order (two calls are
+ * bitwise equal); nothing synchronises inside the loop.  Ns <= 512 runs the
+ * loop in one launch of one workgroup (environment PDSC_ICP_ONE_WG=0, read at
+ * every call, keeps the launch-per-step path; the results are bitwise the
+ * same).  Like the f4 entry points it synchronises `stream` once at the end to
+ * report the grid error (target extent / max_distance >= 2^21 cells:
+ * PDSC_ERR_ARG, outputs unspecified).  source [Ns,3], target [Nt,3] fp32.   */
+typedef struct pdsc_icp_result { /* device memory, written by the call */
+    double trans[16];            /* final T, fp64 row-major */
+    double fitness, inlier_rmse;
+    int32_t iterations;          /* updates applied, 0 .. max_iteration */
+    int32_t n_corr;
+} pdsc_icp_result;
+size_t pdsc_icp_workspace_bytes(int32_t Ns, int32_t Nt);
+int32_t pdsc_icp_point_to_point(const float *source, int32_t Ns, const float *target, int32_t Nt,
+                                const double *init_trans /* device double[16], NULL = identity */,
+                                double max_distance, int32_t max_iteration, double relative_fitness,
+                                double relative_rmse, float *trans_f32 /* [4,4] = (float)result.trans, may be NULL */,
+                                pdsc_icp_result *result /* may be NULL */,
+                                int32_t *corr /* [Ns] of the final evaluate: target index or -1, may be NULL */,
+                                void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+
 /* ----------------------------------------------- full testing forward ------
  * PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197)
  * for B independent pairs: compat -> encoder -> classifier -> seeds -> kNN ->

@@ -114,6 +114,9 @@ _PROTOS = {
     "pdsc_voxel_down_sample": (c_int32, [vp, vp, c_int32, c_float, vp, vp, vp, vp, c_size_t, vp]),
     "pdsc_compute_fpfh_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "pdsc_compute_fpfh": (c_int32, [vp, vp, c_int32, c_float, c_int32, vp, vp, vp, c_size_t, vp]),
+    "pdsc_icp_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "pdsc_icp_point_to_point": (c_int32, [vp, c_int32, vp, c_int32, vp, c_double, c_int32, c_double, c_double, vp, vp,
+                                          vp, vp, c_size_t, vp]),
     "pdsc_forward_training_workspace_bytes": (c_size_t, [CFG, c_int32, c_int32]),
     "pdsc_range_status": (c_int32, [vp, c_int32, ctypes.POINTER(c_int32), vp]),
     "pdsc_range_poll": (c_int32, [vp, c_int32, vp]),

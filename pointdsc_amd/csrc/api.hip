@@ -1224,6 +1224,33 @@ int32_t pdsc_compute_fpfh(const float *pts, const float *normals, int32_t n, flo
     return grid_status(G, s);
 }
 
+// ------------------------------------------------------- f5 ICP refinement
+size_t pdsc_icp_workspace_bytes(int32_t Ns, int32_t Nt) { return Ns < 1 || Nt < 1 ? 0 : icp_workspace_bytes(Ns, Nt); }
+
+// PDSC_ICP_ONE_WG=0: the launch-per-step path at every size (read at every call)
+static bool icp_one_wg() {
+    const char *e = getenv("PDSC_ICP_ONE_WG");
+    return !(e && e[0] == '0');
+}
+
+int32_t pdsc_icp_point_to_point(const float *source, int32_t Ns, const float *target, int32_t Nt,
+                                const double *init_trans, double max_distance, int32_t max_iteration,
+                                double relative_fitness, double relative_rmse, float *trans_f32,
+                                pdsc_icp_result *result, int32_t *corr, void *ws, size_t ws_bytes,
+                                pdsc_stream_t stream) {
+    if (Ns < 1 || Nt < 1) return fail(PDSC_ERR_ARG, "Ns=%d Nt=%d (need >= 1)", Ns, Nt);
+    if (!(max_distance > 0.0) || !std::isfinite(max_distance))
+        return fail(PDSC_ERR_ARG, "max_distance %g must be > 0 and finite", max_distance);
+    if (max_iteration < 0) return fail(PDSC_ERR_ARG, "max_iteration=%d", max_iteration);
+    if (!source || !target || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_icp_workspace_bytes(Ns, Nt)));
+    hipStream_t s = S_(stream);
+    GridBufs G;
+    HIPCHK(launch_icp(source, Ns, target, Nt, init_trans, max_distance, max_iteration, relative_fitness, relative_rmse,
+                      icp_one_wg(), trans_f32, result, corr, ws, G, s));
+    return grid_status(G, s);
+}
+
 // ------------------------------------------------- f1 correspondence construction
 size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
     return align_bytes((size_t)Ns * 8) + align_bytes((size_t)Nt * 8);

@@ -40,7 +40,7 @@
 namespace pdsc {
 
 typedef unsigned long long u64;
-constexpr int KEY_BITS = 21;
+constexpr int KEY_BITS = GRID_KEY_BITS;
 constexpr long long KEY_MAX = (1LL << KEY_BITS) - 1;
 
 PDSC_DEV u64 pack_key(long long ix, long long iy, long long iz) {

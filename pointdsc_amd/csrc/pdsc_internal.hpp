@@ -318,6 +318,17 @@ hipError_t launch_fpfh(const float *pts, const float *nrm, int n, const int *nbr
                        int K, double *spfh, double *out, float *outn, hipStream_t s);
 int ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t *n_out, std::string &err);
 
+// ICP refinement (icp.hip, the reference drivers' "+ICP" stage)
+constexpr int GRID_KEY_BITS = 21;       // bits per axis of a grid cell key (descriptors.hip: KEY_BITS)
+constexpr int ICP_CHUNK = 256;          // source points per partial row (the fixed summation order)
+constexpr int ICP_ONE_WG_MAX = 512;     // Ns up to which the loop runs in one workgroup (the measured crossover)
+size_t icp_workspace_bytes(int Ns, int Nt);
+// Builds the target's grid (G: for the caller's grid_status) and enqueues the
+// loop; one_wg: take the one-workgroup path where Ns <= ICP_ONE_WG_MAX.
+hipError_t launch_icp(const float *src, int Ns, const float *tgt, int Nt, const double *init, double max_distance,
+                      int max_iter, double rel_fitness, double rel_rmse, bool one_wg, float *trans_f32,
+                      pdsc_icp_result *res, int *corr, void *ws, GridBufs &G, hipStream_t s);
+
 // correspondence construction (corr.hip)
 #define HIP_RET(expr)                         \
     do {                                      \
