@@ -429,6 +429,95 @@ int32_t pdsc_icp_point_to_point(const float *source, int32_t Ns, const float *ta
                                 int32_t *corr /* [Ns] of the final evaluate: target index or -1, may be NULL */,
                                 void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
 
+/* ------------------------------------------ f6 RANSAC on correspondences ---
+ * open3d's registration_ransac_based_on_correspondence with
+ * TransformationEstimationPointToPoint(False), as the reference's drivers call
+ * it (baseline_scripts/baseline_3DMatch.py:80-98: ransac_n 4, 1000 iterations;
+ * evaluation/test_3DMatch.py:59-77, test.py:137-155: ransac_n 3, 5000;
+ * algorithms/FR.py:122-150: ransac_n 4, up to 500000, edge-length checker and /
+ * or confidence).  open3d's algorithm is restated (open3d is not a dependency,
+ * its sampler is not reproducible: parity with open3d itself is unpinned) and
+ * the choices it leaves open are fixed, so that two calls are bitwise equal and
+ * a CPU restatement can follow the draws one by one.  Row i of src [N,3]
+ * corresponds to row i of tgt [N,3] (fp32); H = max_iteration hypotheses h = 0
+ * .. H - 1.
+ *   Sampling    draw j (0 .. ransac_n - 1) of hypothesis h is u = mix64(seed +
+ *               (8 h + j) * 0x9E3779B97F4A7C15) in wrapping 64-bit arithmetic,
+ *               mix64 the splitmix64 finaliser (z += 0x9E3779B97F4A7C15; z = (z ^
+ *               (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) *
+ *               0x94D049BB133111EB; z ^ (z >> 31)); the sample index is ((u >>
+ *               32) * N) >> 32.  Integer arithmetic only.  A hypothesis with a
+ *               repeated index is invalid (count -1).
+ *   Checker     with edge_similarity = sim > 0 (open3d's
+ *               CorrespondenceCheckerBasedOnEdgeLength; its default is 0.9): for
+ *               every pair a < b of the sample, |s_a - s_b| >= sim |t_a - t_b|
+ *               and |t_a - t_b| >= sim |s_a - s_b| in fp64; a hypothesis that
+ *               fails has count -2 and nothing else is computed for it.
+ *   Estimate    unit-weight Kabsch of the ransac_n pairs in fp64: centroids c_A,
+ *               c_B, H = sum (a - c_A)(b - c_B)^T, R = V diag(1, 1, det(V U^T))
+ *               U^T, t = c_B - R c_A.  H is accumulated with compensated sums
+ *               and R refined by one Newton step, so the pose is good to fp64
+ *               rounding for nearly collinear samples too (an fp64 SVD alone
+ *               is off by eps sigma_1 / sigma_2).
+ *   Score       over all N correspondences d^2 = |R s + t - tgt|^2 in fp64; an
+ *               inlier has d^2 < max_distance^2; count = the inliers, sumsq =
+ *               sum of d^2 over them in a fixed order.
+ *   Best        the highest count; among equal counts the lower sumsq; among
+ *               equal sumsq the lower h (open3d's "fitness greater, or equal and
+ *               rmse lower" scan in hypothesis order).
+ *   Rounds      hypotheses are processed in rounds of pdsc_ransac_round().
+ *               After round r = 0, 1, .., with f = best count / N: when
+ *               confidence < 1 and f > 0, stop if (r + 1) round >= log(1 -
+ *               confidence) / log(1 - f^ransac_n), or if f = 1 (the
+ *               criterion's log(0)): open3d's confidence criterion evaluated at
+ *               round granularity.  confidence = 1 never stops early.  The
+ *               round size is therefore part of the result's definition.
+ *               Nothing synchronises inside the loop: every round is enqueued up
+ *               front and the rounds after the stop return at entry.
+ *   Result      labels [N] = 1 for the inliers of the winning hypothesis, else
+ *               0; fitness = n_inliers / N and inlier_rmse = sqrt(sumsq /
+ *               n_inliers) (0 without inliers) refer to it.  With refit != 0
+ *               trans is one fp64 Kabsch over all those inliers
+ *               (algorithms/FR.py:101-114); labels, fitness and inlier_rmse stay
+ *               the winner's.  Without a valid hypothesis trans is the
+ *               identity, fitness 0, labels 0, best -1.  trans_f32 [4,4] =
+ *               (float)trans.
+ *   Errors      PDSC_ERR_UNSUPPORTED for ransac_n other than 3 or 4;
+ *               PDSC_ERR_ARG for N < ransac_n, max_iteration < 1, max_distance
+ *               <= 0 or not finite, confidence outside (0, 1], edge_similarity
+ *               outside [0, 1], null src / tgt / workspace, a workspace that is
+ *               too small: all checked on the host before any device work.
+ *   Left out    open3d 0.9's max_validation: every driver sets it equal to
+ *               max_iteration.  open3d's distance and normal checkers.
+ * Debug rows of hypotheses never drawn (after an early stop) have count -3;
+ * samples are written for every drawn hypothesis, trans / sumsq only for valid
+ * ones (the other rows are left as the caller filled them).                 */
+typedef struct pdsc_ransac_result {   /* device memory */
+    double trans[16];                 /* fp64 row-major, source -> target */
+    double fitness, inlier_rmse;      /* n_inliers / N, sqrt(sum d^2 / n_inliers) (0 if none) */
+    int32_t n_inliers;
+    int32_t iterations;               /* hypotheses drawn: a multiple of the round, or max_iteration */
+    int32_t best;                     /* index of the winning hypothesis, -1: none valid */
+    int32_t n_validated;              /* hypotheses that passed sampling + checker */
+} pdsc_ransac_result;
+typedef struct pdsc_ransac_debug {    /* any member may be NULL; H = max_iteration */
+    int32_t *samples;                 /* [H, ransac_n] */
+    int32_t *count;                   /* [H]: inliers, -1 repeated index, -2 checker, -3 not drawn (early stop) */
+    double  *sumsq;                   /* [H]: sum of d^2 over the inliers */
+    double  *trans;                   /* [H,16] */
+} pdsc_ransac_debug;
+int32_t pdsc_ransac_round(void);      /* hypotheses per round */
+size_t  pdsc_ransac_workspace_bytes(int32_t N);      /* independent of max_iteration */
+int32_t pdsc_ransac_correspondence(const float *src, const float *tgt, int32_t N,
+                                   double max_distance, int32_t ransac_n /* 3 or 4 */,
+                                   double edge_similarity /* 0: no checker */,
+                                   int32_t max_iteration, double confidence /* 1.0: never stop early */,
+                                   uint64_t seed, int32_t refit, float *trans_f32 /* may be NULL */,
+                                   float *labels /* [N] 0/1, may be NULL */,
+                                   pdsc_ransac_result *result /* may be NULL */,
+                                   const pdsc_ransac_debug *debug /* HOST struct of device pointers, may be NULL */,
+                                   void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+
 /* ----------------------------------------------- full testing forward ------
  * PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197)
  * for B independent pairs: compat -> encoder -> classifier -> seeds -> kNN ->

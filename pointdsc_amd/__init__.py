@@ -3,15 +3,22 @@
 ``pointdsc_amd.PointDSC.PointDSC`` is the drop-in for the reference's
 ``models.PointDSC.PointDSC``; ``pointdsc_amd.kernels`` exposes each hot-path op;
 ``pointdsc_amd.icp`` refines a pose by point-to-point ICP (the drivers' "+ICP"
-row); the C ABI is ``include/pdsc.h`` / ``pointdsc_amd/libpdsc.so``.
+row); ``pointdsc_amd.ransac`` is RANSAC on correspondences (the drivers' RANSAC
+baseline and ``--solver RANSAC``); the C ABI is ``include/pdsc.h`` /
+``pointdsc_amd/libpdsc.so``.
 """
 __version__ = "0.1.0"
 
-__all__ = ["icp_refine", "registration_icp"]
+_ICP = ("icp_refine", "registration_icp")
+_RANSAC = ("registration_ransac_based_on_correspondence", "ransac_solver")
+__all__ = [*_ICP, *_RANSAC]
 
 
-def __getattr__(name):  # the ICP entry points, without importing torch on `import pointdsc_amd`
-    if name in __all__:
+def __getattr__(name):  # the ICP / RANSAC entry points, without importing torch on `import pointdsc_amd`
+    if name in _ICP:
         from . import icp
         return getattr(icp, name)
+    if name in _RANSAC:
+        from . import ransac
+        return getattr(ransac, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -55,6 +55,11 @@ class PdscForwardDebug(ctypes.Structure):
     _fields_ = [("conf", vp), ("seeds", vp), ("knn", vp), ("weights", vp), ("trans_pre_refine", vp)]
 
 
+class PdscRansacDebug(ctypes.Structure):
+    """``struct pdsc_ransac_debug`` (include/pdsc.h): optional per-hypothesis outputs."""
+    _fields_ = [("samples", vp), ("count", vp), ("sumsq", vp), ("trans", vp)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "pdsc_version": (ctypes.c_char_p, []),
@@ -117,6 +122,11 @@ _PROTOS = {
     "pdsc_icp_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "pdsc_icp_point_to_point": (c_int32, [vp, c_int32, vp, c_int32, vp, c_double, c_int32, c_double, c_double, vp, vp,
                                           vp, vp, c_size_t, vp]),
+    "pdsc_ransac_round": (c_int32, []),
+    "pdsc_ransac_workspace_bytes": (c_size_t, [c_int32]),
+    "pdsc_ransac_correspondence": (c_int32, [vp, vp, c_int32, c_double, c_int32, c_double, c_int32, c_double,
+                                             ctypes.c_uint64, c_int32, vp, vp, vp, ctypes.POINTER(PdscRansacDebug),
+                                             vp, c_size_t, vp]),
     "pdsc_forward_training_workspace_bytes": (c_size_t, [CFG, c_int32, c_int32]),
     "pdsc_range_status": (c_int32, [vp, c_int32, ctypes.POINTER(c_int32), vp]),
     "pdsc_range_poll": (c_int32, [vp, c_int32, vp]),

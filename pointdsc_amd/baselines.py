@@ -37,6 +37,25 @@ def SM(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, top_ratio: 
     return (trans, labels, eig) if return_eig else (trans, labels)
 
 
+def RANSAC(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, max_iteration: int = 1000, seed: int = 0):
+    """baseline_scripts/baseline_3DMatch.py:80-98: RANSAC with ransac_n = 4 over
+    every correspondence (``corr`` is accepted for the baselines' common
+    signature and not read, as there), ``args.inlier_threshold`` and
+    ``args.max_iteration`` passed as keywords.  Same outputs as ``SM``:
+    ``(pred_trans [1,4,4], pred_labels [1,N])``.  Runs on
+    pointdsc_amd/csrc/ransac.hip (pdsc_ransac_correspondence); ``seed`` fixes the
+    draws.  No CPU fallback."""
+    from .ransac import registration_ransac_based_on_correspondence
+    src, tgt = _dev(src_keypts, "src_keypts"), _dev(tgt_keypts, "tgt_keypts")
+    assert src.shape[0] == 1, "RANSAC: bs = 1 (baseline_3DMatch.py:81-82)"
+    N = src.shape[1]
+    if src.shape != (1, N, 3) or tgt.shape != (1, N, 3):
+        raise ValueError(f"shapes {tuple(src.shape)} {tuple(tgt.shape)}")
+    res = registration_ransac_based_on_correspondence(src[0], tgt[0], None, inlier_threshold, ransac_n=4,
+                                                      max_iteration=max_iteration, seed=seed)
+    return res.transformation_f32[None], res.labels[None]
+
+
 def sm_matvec(M, v):
     """y = M v (one SM power-iteration product; M [N,N], v [N])."""
     M, v = _dev(M, "M"), _dev(v, "v")

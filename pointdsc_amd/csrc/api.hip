@@ -1251,6 +1251,32 @@ int32_t pdsc_icp_point_to_point(const float *source, int32_t Ns, const float *ta
     return grid_status(G, s);
 }
 
+// ------------------------------------------------ f6 RANSAC on correspondences
+int32_t pdsc_ransac_round(void) { return RANSAC_ROUND; }
+
+size_t pdsc_ransac_workspace_bytes(int32_t N) { return N < 1 ? 0 : ransac_workspace_bytes(N); }
+
+int32_t pdsc_ransac_correspondence(const float *src, const float *tgt, int32_t N, double max_distance,
+                                   int32_t ransac_n, double edge_similarity, int32_t max_iteration,
+                                   double confidence, uint64_t seed, int32_t refit, float *trans_f32, float *labels,
+                                   pdsc_ransac_result *result, const pdsc_ransac_debug *debug, void *ws,
+                                   size_t ws_bytes, pdsc_stream_t stream) {
+    if (ransac_n != 3 && ransac_n != 4)
+        return fail(PDSC_ERR_UNSUPPORTED, "ransac_n=%d: only 3 and 4 are implemented", ransac_n);
+    if (N < ransac_n) return fail(PDSC_ERR_ARG, "N=%d < ransac_n=%d", N, ransac_n);
+    if (max_iteration < 1) return fail(PDSC_ERR_ARG, "max_iteration=%d (need >= 1)", max_iteration);
+    if (!(max_distance > 0.0) || !std::isfinite(max_distance))
+        return fail(PDSC_ERR_ARG, "max_distance %g must be > 0 and finite", max_distance);
+    if (!(confidence > 0.0 && confidence <= 1.0)) return fail(PDSC_ERR_ARG, "confidence %g not in (0, 1]", confidence);
+    if (!(edge_similarity >= 0.0 && edge_similarity <= 1.0))
+        return fail(PDSC_ERR_ARG, "edge_similarity %g not in [0, 1]", edge_similarity);
+    if (!src || !tgt || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_ransac_workspace_bytes(N)));
+    HIPCHK(launch_ransac(src, tgt, N, max_distance, ransac_n, edge_similarity, max_iteration, confidence, seed,
+                         refit ? 1 : 0, trans_f32, labels, result, debug, ws, S_(stream)));
+    return PDSC_OK;
+}
+
 // ------------------------------------------------- f1 correspondence construction
 size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
     return align_bytes((size_t)Ns * 8) + align_bytes((size_t)Nt * 8);

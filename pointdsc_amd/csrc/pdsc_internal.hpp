@@ -329,8 +329,16 @@ hipError_t launch_icp(const float *src, int Ns, const float *tgt, int Nt, const 
                       int max_iter, double rel_fitness, double rel_rmse, bool one_wg, float *trans_f32,
                       pdsc_icp_result *res, int *corr, void *ws, GridBufs &G, hipStream_t s);
 
+// RANSAC on correspondences (ransac.hip, the drivers' RANSAC baseline / solver)
+constexpr int RANSAC_ROUND = 16384;     // hypotheses per round: part of the result's definition (pdsc_ransac_round)
+size_t ransac_workspace_bytes(int N);
+// Enqueues every round and the finish; H = max_iteration, sim = edge_similarity.
+hipError_t launch_ransac(const float *src, const float *tgt, int N, double max_distance, int ransac_n, double sim,
+                         int H, double confidence, unsigned long long seed, int refit, float *trans_f32, float *labels,
+                         pdsc_ransac_result *res, const pdsc_ransac_debug *debug, void *ws, hipStream_t s);
+
 // correspondence construction (corr.hip)
-#define HIP_RET(expr)                         \
+#define HIP_RET(expr)                        \
     do {                                      \
         hipError_t e_ = (expr);               \
         if (e_ != hipSuccess) return e_;      \
