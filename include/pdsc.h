@@ -178,6 +178,29 @@ int32_t pdsc_encoder_plan(int32_t B, int32_t N, int32_t precision, int32_t *fuse
 /* *vfold = 1 when that plan folds fc_message[0] into the V projection (a
  * 64-channel V' = (W0 Wv) x and P.V; the PDSC_VFOLD=0 knob: never), else 0.  */
 int32_t pdsc_encoder_plan_vfold(int32_t B, int32_t N, int32_t precision, int32_t *vfold);
+/* Which pointwise-chain and tail kernels pdsc_forward_testing / _training
+ * launch for B pairs of N correspondences under cfg (S = int(N * ratio) seeds,
+ * cfg's precision) and this process's knobs; host-only, touches no device.
+ * out[0 .. PDSC_LAUNCH_PLAN_FIELDS), capacity >= PDSC_LAUNCH_PLAN_FIELDS:
+ *  [0] the pointwise chain: 1 register-chained (pw2_*), 0 LDS-tiled (pw_*);
+ *      [1] .. [5] describe the LDS-tiled chain and are 0 under [0] = 1
+ *  [1] its points per workgroup, 32 or 64
+ *  [2] 1: pw_mid on 8 waves
+ *  [3] 1: pw_first's Q / K / V in three workgroups per point tile
+ *  [4] 1: the 8-wave pw_mid's likewise
+ *  [5] 1: the 8-wave pw_mid's panel prefetch
+ *  [6] rows per block of the NMS / seed-ranking compare kernels, 16 or 64
+ *  [7] the NMS: compare with 1, 2 or 4 rows per thread; 0: the sorted form
+ *  [8] the seed ranking: 0 compare, 1 sorted, 2 select, 3 select with the
+ *      candidate ranking as a second launch (where the caller gives scratch,
+ *      as the forwards do)
+ *  [9] waves (seeds) per workgroup of the seed kNN select, the NSM and the
+ *      hypotheses' sums: 1, 2 or 4
+ * [10] the kNN select's ranking argument (0: readlane compare, else bitonic)
+ * [11] 1: the Kabsch solve and inlier count inside the hypotheses' sums launch
+ * [12] 1: the testing forward's fused tail launches                           */
+#define PDSC_LAUNCH_PLAN_FIELDS 13
+int32_t pdsc_launch_plan(const pdsc_config *cfg, int32_t B, int32_t N, int32_t *out, int32_t capacity);
 /* Where one dense block of a layer sits in the packed blob (tests, tools):
  * block 0..7 = PointCN, fc_message 0 / 3 / 6, projection q / k / v, and the
  * folded W0 Wv block; offsets (in floats) of its weights, bias, BatchNorm

@@ -79,6 +79,7 @@ _PROTOS = {
                                         ctypes.POINTER(c_int32)]),
     "pdsc_encoder_plan": (c_int32, [c_int32, c_int32, c_int32, ctypes.POINTER(c_int32)]),
     "pdsc_encoder_plan_vfold": (c_int32, [c_int32, c_int32, c_int32, ctypes.POINTER(c_int32)]),
+    "pdsc_launch_plan": (c_int32, [CFG, c_int32, c_int32, ctypes.POINTER(c_int32), c_int32]),
     "pdsc_packed_block": (c_int32, [CFG, c_int32, c_int32, ctypes.POINTER(c_size_t)]),
     "pdsc_attention_timing": (c_int32, [ctypes.POINTER(vp), ctypes.POINTER(vp), c_int32, ctypes.POINTER(c_int32)]),
     "pdsc_forward_timing": (c_int32, [ctypes.POINTER(vp), c_int32, ctypes.POINTER(c_int32)]),

@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "attention_plan.hpp"
+#include "launch_plan.hpp"
 #include "pdsc_internal.hpp"
 
 using namespace pdsc;
@@ -82,7 +82,8 @@ int check_cfg(const pdsc_config *cfg) {
 struct Dims {
     int B, N, Npad, S, k, T;
     bool f32;          // PDSC_PRECISION_F32
-    EncoderPlan plan;  // the encoder's attention plan for (B, N, f32)
+    EncoderPlan plan;  // the encoder's plan for (B, N, f32)
+    TailPlan tail;     // the tail's plan for (B, N, S)
 };
 
 // dense_m_caller: the standalone encoder's plan, on the caller's dense M (plan_encoder)
@@ -97,6 +98,7 @@ int make_dims(const pdsc_config *cfg, int B, int N, Dims &d, bool dense_m_caller
     d.T = cfg->num_iterations;
     d.f32 = cfg->precision == PDSC_PRECISION_F32;
     d.plan = plan_encoder(B, N, d.f32, dense_m_caller);
+    d.tail = plan_tail(B, N, d.S);
     if (d.S < 1) return fail(PDSC_ERR_ARG, "int(N*ratio) = 0 seeds for N=%d", N);
     if (d.k > 63) return fail(PDSC_ERR_UNSUPPORTED, "k=%d > 63", d.k);
     return PDSC_OK;
@@ -143,8 +145,7 @@ int run_encoder(const PackLayout &lay, const float *packed, const float *corr_po
                 const EncBufs &e, float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
                 Ragged rg = {}) {
     const EncoderPlan plan = d.plan.for_ragged(rg);
-    HIPCHK(launch_pw_first(packed, lay, corr_pos, d.f32, d.B, d.N, d.Npad, e.feat, e.q, e.k, e.v, e.vexp, s, rg,
-                           plan.fused(), plan.vfold));
+    HIPCHK(launch_pw_first(plan, packed, lay, corr_pos, e.feat, e.q, e.k, e.v, e.vexp, s, rg));
     if (plan.fused()) {  // every layer fused (0 .. L-2 with the next layer's PointCN/QKV, Q/K/V alternating between the two sets)
         _Float16 *q = e.q, *k = e.k, *v = e.v, *q2 = e.q2, *k2 = e.k2, *v2 = e.v2;
         float *vx = e.vexp, *vx2 = e.vexp2;
@@ -176,12 +177,11 @@ int run_encoder(const PackLayout &lay, const float *packed, const float *corr_po
             ns = 1;
         }
         if (l + 1 < lay.L) {
-            HIPCHK(launch_pw_mid(packed, lay, l, d.f32, op, mlp, ns, d.B, d.N, d.Npad, feat, feat_alt, e.q, e.k, e.v,
-                                 e.vexp, s, plan.vfold));
+            HIPCHK(launch_pw_mid(plan, packed, lay, l, op, mlp, ns, feat, feat_alt, e.q, e.k, e.v, e.vexp, s));
             std::swap(feat, feat_alt);
         } else {
-            HIPCHK(launch_pw_last(packed, lay, d.f32, op, mlp, ns, d.B, d.N, d.Npad, feat, feat_out, normed,
-                                  d.f32 ? nullptr : normed_s, conf, s, plan.vfold));
+            HIPCHK(launch_pw_last(plan, packed, lay, op, mlp, ns, feat, feat_out, normed, d.f32 ? nullptr : normed_s,
+                                  conf, s));
         }
     }
     return PDSC_OK;
@@ -200,35 +200,9 @@ int run_encoder(const PackLayout &lay, const float *packed, const float *corr_po
 // on one stream.  Knobs: PDSC_ENC_HALVES 0 never, 1 uniform batches too;
 // PDSC_ENC_PARTS P in [2, 4] (default 2).  Every part keeps the whole batch's
 // plan (the fused launches' one key split, pw2_first's layouts).
-static int enc_halves_mode() {
-    static const int v = [] {
-        const char *e = getenv("PDSC_ENC_HALVES");
-        return e && e[0] == '0' ? 0 : (e && e[0] == '1' ? 2 : 1);
-    }();
-    return v;
-}
-constexpr int ENC_MAX_PARTS = 4;
-static int enc_parts() {
-    static const int v = [] {
-        const char *e = getenv("PDSC_ENC_PARTS");
-        const int p = e ? atoi(e) : 2;
-        return std::min(std::max(p, 2), ENC_MAX_PARTS);
-    }();
-    return v;
-}
-// Parts of equal pair counts; A/B knob PDSC_ENC_BAL=1: parts of equal work
-// sum(n^2) instead (measured slower: 128 pairs, N in [700, 1300], 4.150 / 4.159
-// vs 4.021 / 4.056 ms per forward, one stream 4.423 / 4.437).
-static bool enc_work_balanced() {
-    static const bool on = [] {
-        const char *e = getenv("PDSC_ENC_BAL");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
 static bool enc_halves(const Dims &d, bool ragged) {
-    const int mode = enc_halves_mode();
-    return d.plan.fused() && d.B >= 16 * enc_parts() && (mode == 2 || (mode == 1 && ragged));
+    const Knobs &k = knobs();
+    return d.plan.fused() && d.B >= 16 * k.enc_parts && (k.enc_halves == 1 || (k.enc_halves != 0 && ragged));
 }
 // Part boundaries bounds[0 .. P]: bounds[i] = the first pair whose work prefix
 // reaches i/P of the total (counts: HOST sizes, or NULL for a uniform batch).
@@ -367,8 +341,8 @@ NsmBufs carve_nsm(Carve &c, int B, int N, int S, int k, int T, bool own_split) {
 
 // normed_s: the split normed copy, or NULL to build it here from normed (H3);
 // f32: the Gram reads normed itself
-int run_nsm(const float *normed, const _Float16 *normed_s, bool f32, const float *src, const float *tgt,
-            const int *knn, int B, int N, int S, int k, int T, const float *sigma, const float *sigma_d,
+int run_nsm(const TailPlan &tp, const float *normed, const _Float16 *normed_s, bool f32, const float *src,
+            const float *tgt, const int *knn, int B, int N, int S, int k, int T, const float *sigma, const float *sigma_d,
             const NsmBufs &nb, float *weights, int *iters, bool batch_global, hipStream_t s, Ragged rg = {}) {
     if (!f32 && !normed_s) {
         HIPCHK(launch_split_rows(normed, (size_t)B * N, nb.ns, s));
@@ -376,30 +350,9 @@ int run_nsm(const float *normed, const _Float16 *normed_s, bool f32, const float
     }
     const void *feats = f32 ? static_cast<const void *>(normed) : static_cast<const void *>(normed_s);
     if (T > 0)
-        HIPCHK(launch_nsm_seed(feats, f32, src, tgt, knn, B, N, S, k, T, sigma, sigma_d, nb.hist, nb.mask, s, rg));
+        HIPCHK(launch_nsm_seed(tp, feats, f32, src, tgt, knn, B, N, S, k, T, sigma, sigma_d, nb.hist, nb.mask, s, rg));
     HIPCHK(launch_nsm_finish(nb.hist, nb.mask, B, S, k, T, batch_global, weights, iters, s, rg));
     return PDSC_OK;
-}
-
-// The testing forward's fused tail launches (nsm_finish inside the hypotheses'
-// first launch, select_best + post_refine in one): the same bits, two launches
-// fewer per forward.  A/B knob PDSC_TAIL_FUSED=0 (measurement only).
-static bool tail_fused() {
-    static const bool off = [] {
-        const char *e = getenv("PDSC_TAIL_FUSED");
-        return e && e[0] == '0';
-    }();
-    return !off;
-}
-
-// A/B knob (measurement only): PDSC_RAGGED_ORDER=0 keeps the ragged attention
-// workgroups in pair order.
-static bool ragged_order_on() {
-    static const bool off = [] {
-        const char *e = getenv("PDSC_RAGGED_ORDER");
-        return e && e[0] == '0';
-    }();
-    return !off;
 }
 
 struct FwdBufs {
@@ -695,6 +648,21 @@ int32_t pdsc_encoder_plan_vfold(int32_t B, int32_t N, int32_t precision, int32_t
     return PDSC_OK;
 }
 
+int32_t pdsc_launch_plan(const pdsc_config *cfg, int32_t B, int32_t N, int32_t *out, int32_t capacity) {
+    RET_IF(check_cfg(cfg));
+    Dims d;
+    RET_IF(make_dims(cfg, B, N, d));
+    if (!out || capacity < PDSC_LAUNCH_PLAN_FIELDS)
+        return fail(PDSC_ERR_ARG, "out=%p capacity=%d (need %d)", (void *)out, capacity, PDSC_LAUNCH_PLAN_FIELDS);
+    const EncoderPlan &p = d.plan;
+    const TailPlan &t = d.tail;
+    const int32_t row[PDSC_LAUNCH_PLAN_FIELDS] = {p.pw2,         p.pw_tile,   p.pw_mid8, p.pw_first_qkv3, p.pw_mid_qkv3,
+                                                  p.pw_prefetch, t.seed_rows, t.nms_rpt, (int32_t)t.rank, t.wpb,
+                                                  t.knn_bitonic, t.kabsch_fused, t.tail_fused};
+    std::copy(row, row + PDSC_LAUNCH_PLAN_FIELDS, out);
+    return PDSC_OK;
+}
+
 int32_t pdsc_packed_block(const pdsc_config *cfg, int32_t layer, int32_t block, size_t offsets[5]) {
     RET_IF(check_cfg(cfg));
     if (layer < 0 || layer >= cfg->num_layers || block < 0 || block > 7 || !offsets)
@@ -712,15 +680,16 @@ int32_t pdsc_pick_seeds(const float *src, const float *conf, int32_t B, int32_t 
     if (!src || !conf || !seeds || !is_local_max) return fail(PDSC_ERR_ARG, "null pointer (is_local_max is used as scratch)");
     if (B < 1 || N < 1 || S < 1 || S > N) return fail(PDSC_ERR_ARG, "B=%d N=%d S=%d", B, N, S);
     hipStream_t s = S_(stream);
-    HIPCHK(launch_local_max(src, conf, B, N, radius, is_local_max, s));
-    HIPCHK(launch_seed_rank(conf, is_local_max, B, N, S, seeds, s));
+    const TailPlan tp = plan_tail(B, N, S);
+    HIPCHK(launch_local_max(tp, src, conf, B, N, radius, is_local_max, s));
+    HIPCHK(launch_seed_rank(tp, conf, is_local_max, B, N, S, seeds, s));
     return PDSC_OK;
 }
 
 // -------------------------------------------------------------------- a6
 // a6 (:250-252) for the forwards: knn [B][S][k]; dist [B][S][N] scratch
-int run_seed_knn(const float *normed, const _Float16 *normed_s, bool f32, const int *seeds, int B, int N, int S,
-                 int k, float *dist, int *knn, hipStream_t s, Ragged rg = {}) {
+int run_seed_knn(const TailPlan &tp, const float *normed, const _Float16 *normed_s, bool f32, const int *seeds, int B,
+                 int N, int S, int k, float *dist, int *knn, hipStream_t s, Ragged rg = {}) {
     // (no zero fill of knn: knn_select writes all k entries of every seed row it
     // owns -- ranks 1 .. k of k + 1 distinct (key, index) candidates -- and the
     // rows past a ragged pair's own seeds are never read; readers clamp indices)
@@ -729,7 +698,7 @@ int run_seed_knn(const float *normed, const _Float16 *normed_s, bool f32, const 
     } else {
         HIPCHK(launch_knn_dist(normed_s, seeds, B, N, S, dist, s, rg));
     }
-    HIPCHK(launch_knn_select(dist, B, N, S, k, knn, s, rg));
+    HIPCHK(launch_knn_select(tp, dist, B, N, S, k, knn, s, rg));
     return PDSC_OK;
 }
 
@@ -752,7 +721,7 @@ int32_t pdsc_seed_knn(const float *normed, const int32_t *seeds, int32_t B, int3
     _Float16 *ns = c.take<_Float16>((size_t)B * N * 2 * CH);
     const bool f32 = precision == PDSC_PRECISION_F32;
     if (!f32) HIPCHK(launch_split_rows(normed, (size_t)B * N, ns, s));
-    return run_seed_knn(normed, ns, f32, seeds, B, N, S, k, dist, knn, s);
+    return run_seed_knn(plan_tail(B, N, S), normed, ns, f32, seeds, B, N, S, k, dist, knn, s);
 }
 
 // ----------------------------------------------------------------- a7-a8
@@ -776,8 +745,8 @@ int32_t pdsc_nsm_weights(const float *normed, const float *src, const float *tgt
     RET_IF(need_ws(ws_bytes, pdsc_nsm_workspace_bytes(B, N, S, k, T)));
     Carve c(ws);
     NsmBufs nb = carve_nsm(c, B, N, S, k, T, true);
-    return run_nsm(normed, nullptr, precision == PDSC_PRECISION_F32, src, tgt, knn, B, N, S, k, T, sigma, sigma_d,
-                   nb, weights, iters, true, S_(stream));
+    return run_nsm(plan_tail(B, N, S), normed, nullptr, precision == PDSC_PRECISION_F32, src, tgt, knn, B, N, S, k, T,
+                   sigma, sigma_d, nb, weights, iters, true, S_(stream));
 }
 
 // -------------------------------------------------------------------- a9
@@ -809,7 +778,7 @@ int32_t pdsc_seed_hypotheses(const float *src, const float *tgt, const int32_t *
     int *counts = reinterpret_cast<int *>(fitness);
     if (!ws || ws_bytes < pdsc_seed_hypotheses_workspace_bytes(B, S))
         return fail(PDSC_ERR_ARG, "workspace too small");
-    HIPCHK(launch_hypotheses(src, tgt, knn, weights, B, N, S, k, tau, seed_trans, counts,
+    HIPCHK(launch_hypotheses(plan_tail(B, N, S), src, tgt, knn, weights, B, N, S, k, tau, seed_trans, counts,
                              static_cast<float *>(ws), s));
     HIPCHK(launch_select_best(src, tgt, seed_trans, counts, B, N, S, tau, fitness, best, trans, labels, s));
     return PDSC_OK;
@@ -871,15 +840,15 @@ static int32_t forward_testing_impl(const pdsc_config *cfg, const float *packed,
     const FwdBufs f = carve_forward(c, d);
     Ragged rg;
     SideStream *halves = enc_halves(d, counts != nullptr) ? side_stream(s) : nullptr;
-    const int parts = halves ? enc_parts() : 1;
+    const int parts = halves ? knobs().enc_parts : 1;
     int bounds[ENC_MAX_PARTS + 1] = {0, B};
-    if (halves) enc_bounds(enc_work_balanced() ? counts : nullptr, B, parts, bounds);
+    if (halves) enc_bounds(knobs().enc_bal ? counts : nullptr, B, parts, bounds);
     if (counts) {
         HIPCHK(launch_ragged_setup(counts, B, cfg->ratio, f.nv, f.sv, s));
         rg.nv = f.nv;
         rg.sv = f.sv;
         rg.eq = std::all_of(counts, counts + B, [N](int32_t n) { return n == N; });
-        if (ragged_order_on()) {  // each part's attention launches order that part's pairs
+        if (knobs().ragged_order) {  // each part's attention launches order that part's pairs
             for (int i = 0; i < parts; ++i)
                 HIPCHK(launch_ragged_order(counts + bounds[i], bounds[i + 1] - bounds[i], f.po + bounds[i], s));
             rg.po = f.po;
@@ -906,28 +875,30 @@ static int32_t forward_testing_impl(const pdsc_config *cfg, const float *packed,
                            bounds, parts));
     STAGE(2);
     // a5 (:174)
-    HIPCHK(launch_local_max(src, f.conf, d.B, d.N, cfg->nms_radius, f.lm, s, rg));
+    HIPCHK(launch_local_max(d.tail, src, f.conf, d.B, d.N, cfg->nms_radius, f.lm, s, rg));
     // (kdist, written by the seed kNN next, is the ranking's scratch)
-    HIPCHK(launch_seed_rank(f.conf, f.lm, d.B, d.N, d.S, f.seeds, s, rg, reinterpret_cast<uint32_t *>(f.kdist)));
+    HIPCHK(launch_seed_rank(d.tail, f.conf, f.lm, d.B, d.N, d.S, f.seeds, s, rg,
+                            reinterpret_cast<uint32_t *>(f.kdist)));
     STAGE(3);
     // a6 (:250-252)
-    RET_IF(run_seed_knn(f.normed, f.normed_s, d.f32, f.seeds, d.B, d.N, d.S, d.k, f.kdist, f.knn, s, rg));
+    RET_IF(run_seed_knn(d.tail, f.normed, f.normed_s, d.f32, f.seeds, d.B, d.N, d.S, d.k, f.kdist, f.knn, s, rg));
     STAGE(4);
     // a7-a8 (:257-282)
     // per pair: each pair is its own bs = 1 forward, whose allclose spans its S seeds.
     // The power iterates here; nsm_finish's step (t*, the normalised weights) runs
     // inside the hypotheses' first launch below (the same bits, one launch fewer).
-    const bool tail = tail_fused();
+    const bool tail = d.tail.tail_fused;
     if (!tail) {
-        RET_IF(run_nsm(f.normed, f.normed_s, d.f32, src, tgt, f.knn, d.B, d.N, d.S, d.k, d.T, sigma, sigma_d, f.nsm,
-                       f.weights, nullptr, false, s, rg));
+        RET_IF(run_nsm(d.tail, f.normed, f.normed_s, d.f32, src, tgt, f.knn, d.B, d.N, d.S, d.k, d.T, sigma, sigma_d,
+                       f.nsm, f.weights, nullptr, false, s, rg));
     } else if (d.T > 0)
-        HIPCHK(launch_nsm_seed(d.f32 ? static_cast<const void *>(f.normed) : static_cast<const void *>(f.normed_s),
+        HIPCHK(launch_nsm_seed(d.tail,
+                               d.f32 ? static_cast<const void *>(f.normed) : static_cast<const void *>(f.normed_s),
                                d.f32, src, tgt, f.knn, d.B, d.N, d.S, d.k, d.T, sigma, sigma_d, f.nsm.hist, f.nsm.mask,
                                s, rg));
     STAGE(5);
     // a9-a10 (:280-282, :287-335)
-    HIPCHK(launch_hypotheses(src, tgt, f.knn, f.weights, d.B, d.N, d.S, d.k, cfg->inlier_threshold,
+    HIPCHK(launch_hypotheses(d.tail, src, tgt, f.knn, f.weights, d.B, d.N, d.S, d.k, cfg->inlier_threshold,
                              f.seed_trans, f.counts, f.hsums, s, rg, tail ? f.nsm.hist : nullptr, f.nsm.mask, d.T,
                              f.weights));
     if (dbg->trans_pre_refine || !tail) {  // the pose before refinement: the two launches
@@ -1005,15 +976,15 @@ int32_t pdsc_forward_training(const pdsc_config *cfg, const float *packed, const
                                d.f32, d.B, d.N, sigma, M_out, s));
     // seeds = argsort(confidence, descending)[:, :S] (:176): the ranking with every flag 1
     HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f.lm), 0x3f800000u, (size_t)d.B * d.N, s));
-    HIPCHK(launch_seed_rank(f.conf, f.lm, d.B, d.N, d.S, f.seeds, s));
+    HIPCHK(launch_seed_rank(d.tail, f.conf, f.lm, d.B, d.N, d.S, f.seeds, s));
     // a6-a10 as in testing (:182 -> cal_seed_trans), no post-refinement (:185-186)
     // (f.counts: the hypotheses' inlier counts later, the overflow flags here)
-    RET_IF(run_seed_knn(f.normed, f.normed_s, d.f32, f.seeds, d.B, d.N, d.S, d.k, f.kdist, f.knn, s));
+    RET_IF(run_seed_knn(d.tail, f.normed, f.normed_s, d.f32, f.seeds, d.B, d.N, d.S, d.k, f.kdist, f.knn, s));
     // the training batch is ONE reference forward: torch.allclose over all B * S seeds (:354)
-    RET_IF(run_nsm(f.normed, f.normed_s, d.f32, src, tgt, f.knn, d.B, d.N, d.S, d.k, d.T, sigma, sigma_d, f.nsm,
+    RET_IF(run_nsm(d.tail, f.normed, f.normed_s, d.f32, src, tgt, f.knn, d.B, d.N, d.S, d.k, d.T, sigma, sigma_d, f.nsm,
                    f.weights, nullptr, true, s));
-    HIPCHK(launch_hypotheses(src, tgt, f.knn, f.weights, d.B, d.N, d.S, d.k, cfg->inlier_threshold, f.seed_trans,
-                             f.counts, f.hsums, s));
+    HIPCHK(launch_hypotheses(d.tail, src, tgt, f.knn, f.weights, d.B, d.N, d.S, d.k, cfg->inlier_threshold,
+                             f.seed_trans, f.counts, f.hsums, s));
     // the labels of the best hypothesis are not returned in training mode (:189-191): f.lm is scratch
     HIPCHK(launch_select_best(src, tgt, f.seed_trans, f.counts, d.B, d.N, d.S, cfg->inlier_threshold, nullptr,
                               nullptr, final_trans, f.lm, s, {}, f.conf, f.range));
@@ -1227,7 +1198,7 @@ int32_t pdsc_compute_fpfh(const float *pts, const float *normals, int32_t n, flo
 // ------------------------------------------------------- f5 ICP refinement
 size_t pdsc_icp_workspace_bytes(int32_t Ns, int32_t Nt) { return Ns < 1 || Nt < 1 ? 0 : icp_workspace_bytes(Ns, Nt); }
 
-// PDSC_ICP_ONE_WG=0: the launch-per-step path at every size (read at every call)
+// PDSC_ICP_ONE_WG=0: the launch-per-step path at every size (not in Knobs: read at every call, tests toggle it)
 static bool icp_one_wg() {
     const char *e = getenv("PDSC_ICP_ONE_WG");
     return !(e && e[0] == '0');

@@ -27,7 +27,7 @@
 
 #include "attention.hpp"
 #include "attention_h3.hpp"
-#include "attention_plan.hpp"
+#include "launch_plan.hpp"
 #include "attention_w64.hpp"
 
 namespace pdsc {
@@ -159,10 +159,19 @@ constexpr int ATT_NW = 4;
 // PDSC_PRECISION_F32: attention.hpp's exact-fp32 MFMA kernel, 32-key stages, libm expf
 constexpr int ATT_F32_KTS = 32;
 
-// The encoder's attention plan (attention_plan.hpp): every rule that picks a
-// kernel and its grid for a shape, each with the measurements behind it.
+// pw2 for launches of at least 320 128-point workgroups, 1.25 per CU.  Measured
+// encoder ms, pw2 vs pw_mid chains: 8 x N=5000 (320 WGs; 3 key splits) 4.48
+// vs 4.61; 40 x 1000 (320, fused) 1.47 vs 1.78; 56 x 1000 (448, fused) 1.68 vs
+// 2.12; 32 x 1000 (256) 1.26 vs 1.22 and 1.24 fused; 16 x 1000 (128) 0.95 vs 0.80.
+static bool use_pw2(const Knobs &k, int B, int Npad, bool f32) {
+    if (f32 || k.pw2 == 0) return false;
+    return k.pw2 == 2 || (long)B * ((Npad + PW2_PTS - 1) / PW2_PTS) >= 320;
+}
+
+// The encoder's plan (launch_plan.hpp): every rule that picks a kernel and its
+// grid for a shape, each with the measurements behind it.
 EncoderPlan plan_encoder(int B, int N, bool f32, bool dense_m_caller, bool allow_fused) {
-    const AttnKnobs &k = attn_knobs();
+    const Knobs &k = knobs();
     EncoderPlan p{};
     p.B = B;
     p.N = N;
@@ -181,7 +190,8 @@ EncoderPlan plan_encoder(int B, int N, bool f32, bool dense_m_caller, bool allow
 
     // attn_pw2 wherever pw2 runs and the attention has one key split
     const AttnGridH3 fg = attention_h3_grid<PW2_W>(B, N, k.target * 4 / PW2_W);
-    const bool fused = allow_fused && k.fuse && use_pw2(B, p.Npad, f32) && fg.nsplit == 1 && fg.nqb * PW2_PTS == p.Npad;
+    p.pw2 = use_pw2(k, B, p.Npad, f32);
+    const bool fused = allow_fused && k.fuse && p.pw2 && fg.nsplit == 1 && fg.nqb * PW2_PTS == p.Npad;
 
     // The 64-query-wave attention (attention_w64.hpp, one 4-wave workgroup per CU,
     // symmetric-packed M) for the split path: from 128 blocks of 256 queries
@@ -260,7 +270,7 @@ EncoderPlan plan_encoder(int B, int N, bool f32, bool dense_m_caller, bool allow
     // 4-wave h3 kernel with the in-kernel combine.  (allow_fused = false: the
     // standalone attention, on the caller's 128-channel V.)
     p.vfold = k.vfold && allow_fused && !f32 &&
-              (fused || (use_pw2(B, p.Npad, f32) && !p.precombine &&
+              (fused || (p.pw2 && !p.precombine &&
                          (p.w64() || (p.kind == ATT_H3 && p.nw == ATT_NW))));
     if (fused) {  // one key split per query block; nsplit stays the split plan's
         p.kind = ATT_FUSED;
@@ -270,6 +280,25 @@ EncoderPlan plan_encoder(int B, int N, bool f32, bool dense_m_caller, bool allow
         p.nqb = fg.nqb;
         p.sps = nst;
     }
+    if (p.pw2) return p;
+
+    // The LDS-tiled pointwise chain's form.
+    // Point-tile size: 64 points (two 32-row MFMA tiles per wave, 2 workgroups per
+    // CU) once the launch has >= 2 workgroups per CU, else 32 (twice the
+    // workgroups for single pairs and small batches).
+    const bool small_tiles = (long)B * (p.Npad / 64) < k.pw_small_limit;
+    p.pw_tile = small_tiles ? 32 : 64;
+    // 8-wave pw_mid workgroups (32 points each) when the launch has at most one
+    // workgroup per CU (a single N = 1000 pair: 32): the chain's output tiles
+    // spread over twice the waves.
+    p.pw_mid8 = !f32 && k.pw_waves8 && (long)B * (p.Npad / 32) <= 256;
+    // Q, K and V in three workgroups per point tile (pcn_qkv8's `only`) while that
+    // stays within one workgroup per CU: pw_first on its 32-point tiles, and the
+    // 8-wave pw_mid.
+    const bool qkv3 = k.pw_qkv_split && 3L * B * (p.Npad / 32) <= 256;
+    p.pw_first_qkv3 = !f32 && small_tiles && qkv3;
+    p.pw_mid_qkv3 = p.pw_mid8 && qkv3;
+    p.pw_prefetch = p.pw_mid8 && k.pw_prefetch;
     return p;
 }
 
@@ -1144,16 +1173,6 @@ PDSC_DEV void mid_split8(float *XA, float *XB, const float *__restrict__ pk, con
         dense_split<SPLIT_V, 1>(Xs, pa, pk, d.v, w4, V, p0, lane, XA, vexp, wave < 4);  // XA is dead
     }
     CH_STAMP(159);
-}
-
-// A/B knob (measurement only): PDSC_PW_PREFETCH=0 runs the Q / K / V split
-// chain without the panel prefetch (message_resid + pcn_qkv8).
-static bool pw_prefetch_on() {
-    static const bool off = [] {
-        const char *e = getenv("PDSC_PW_PREFETCH");
-        return e && e[0] == '0';
-    }();
-    return !off;
 }
 
 template <int PTT, bool F32, int NWV = 4>
@@ -2137,72 +2156,37 @@ hipError_t launch_attn_pw2_last(const EncoderPlan &plan, const float *packed, co
     return hipGetLastError();
 }
 
-// Point-tile size: 64 points (two 32-row MFMA tiles per wave, 2 workgroups per
-// CU) once the launch has >= 2 workgroups per CU, else 32 (twice the
-// workgroups for single pairs and small batches).
-static bool small_tiles(int B, int Npad) {
-    static const long lim = [] {  // A/B knob (measurement only): PDSC_PW_SMALL_LIMIT
-        const char *e = getenv("PDSC_PW_SMALL_LIMIT");
-        return e ? atol(e) : 512L;
-    }();
-    return (long)B * (Npad / 64) < lim;
-}
-
-// 8-wave pw_mid workgroups (32 points each) when the launch has at most one
-// workgroup per CU (a single N = 1000 pair: 32): the chain's output tiles
-// spread over twice the waves (A/B knob PDSC_PW_WAVES=4: never).
-static bool pw_waves8(int B, int Npad) {
-    static const bool off = [] {
-        const char *e = getenv("PDSC_PW_WAVES");
-        return e && atoi(e) == 4;
-    }();
-    return !off && (long)B * (Npad / 32) <= 256;
-}
-
-// 8-wave pw_mid with Q, K and V in three workgroups per point tile (pcn_qkv8's
-// `only`) while that stays within one workgroup per CU.  A/B knob
-// PDSC_PW_QKV_SPLIT=0 (measurement only; the same bits either way).
-static bool pw_qkv_split(int B, int Npad) {
-    static const bool off = [] {
-        const char *e = getenv("PDSC_PW_QKV_SPLIT");
-        return e && e[0] == '0';
-    }();
-    return !off && 3L * B * (Npad / 32) <= 256;
-}
-
-// One launch of pointwise kernel K<PTT, F32> with PTT and F32 picked at run time.
+// One launch of pointwise kernel K<PTT, F32> with the plan's PTT and F32.
 #define PW_LAUNCH(K, rows, ...)                                                                         \
     do {                                                                                                \
-        const bool st_ = small_tiles(B, Npad);                                                          \
-        const int pt_ = st_ ? 32 : 64;                                                                  \
-        const dim3 g_(((rows) + pt_ - 1) / pt_, B);                                                     \
-        if (st_ && f32)                                                                                 \
+        const bool st_ = plan.pw_tile == 32;                                                            \
+        const dim3 g_(((rows) + plan.pw_tile - 1) / plan.pw_tile, plan.B);                              \
+        if (st_ && plan.f32)                                                                            \
             hipLaunchKernelGGL((K<32, true>), g_, dim3(256), pw_lds<32>(), s, __VA_ARGS__);             \
         else if (st_)                                                                                   \
             hipLaunchKernelGGL((K<32, false>), g_, dim3(256), pw_lds<32>(), s, __VA_ARGS__);            \
-        else if (f32)                                                                                   \
+        else if (plan.f32)                                                                              \
             hipLaunchKernelGGL((K<64, true>), g_, dim3(256), pw_lds<64>(), s, __VA_ARGS__);             \
         else                                                                                            \
             hipLaunchKernelGGL((K<64, false>), g_, dim3(256), pw_lds<64>(), s, __VA_ARGS__);            \
     } while (0)
 
-hipError_t launch_pw_first(const float *packed, const PackLayout &lay, const float *corr_pos, bool f32, int B,
-                           int N, int Npad, float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s,
-                           Ragged rg, bool fused, bool vfold) {
+hipError_t launch_pw_first(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *corr_pos,
+                           float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s, Ragged rg) {
     if (lay.in_dim > IN_LIMIT) return hipErrorInvalidValue;
+    const int B = plan.B, N = plan.N, Npad = plan.Npad;
     _Float16 *Q = static_cast<_Float16 *>(q), *K = static_cast<_Float16 *>(k), *V = static_cast<_Float16 *>(v);
-    if (fused || use_pw2(B, Npad, f32)) {  // the fused plan's layouts (a part of a batch: the batch's plan)
-        const PwDense4 d = dense4(lay.layer[0], vfold);
-        const W2Sched S = sched_qkv(W2Sched{}, d, vfold);
-        with_bool(vfold, [&](auto vf) {
+    if (plan.pw2) {  // the fused plan's layouts
+        const PwDense4 d = dense4(lay.layer[0], plan.vfold);
+        const W2Sched S = sched_qkv(W2Sched{}, d, plan.vfold);
+        with_bool(plan.vfold, [&](auto vf) {
             hipLaunchKernelGGL(pw2_first_kernel<decltype(vf)::value>, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B),
                                dim3(PW2_W * 64), PW2_LDS, s, packed, S, lay.l0_w, lay.l0_b, d, corr_pos, lay.in_dim, N,
-                               Npad, feat, Q, K, V, vexp, rg.nv, (int)!fused);
+                               Npad, feat, Q, K, V, vexp, rg.nv, (int)!plan.fused());
         });
         return hipGetLastError();
     }
-    if (vfold) return hipErrorInvalidValue;  // the register-chained kernels only
-    if (!f32 && small_tiles(B, Npad) && pw_qkv_split(B, Npad)) {  // Q / K / V in three workgroups per tile
+    if (plan.pw_first_qkv3) {  // Q / K / V in three workgroups per tile
         hipLaunchKernelGGL((pw_first_kernel<32, false>), dim3(Npad / 32, B, 3), dim3(256), pw_lds<32>(), s, packed,
                            lay.l0_w, lay.l0_b, dense4(lay.layer[0]), corr_pos, lay.in_dim, N, Npad, feat, Q, K, V, vexp,
                            rg.nv);
@@ -2213,28 +2197,28 @@ hipError_t launch_pw_first(const float *packed, const PackLayout &lay, const flo
     return hipGetLastError();
 }
 
-hipError_t launch_pw_mid(const float *packed, const PackLayout &lay, int layer, bool f32, const float *opart,
-                         const float *ml, int nsplit, int B, int N, int Npad, const float *feat_in, float *feat,
-                         void *q, void *k, void *v, float *vexp, hipStream_t s, bool vfold) {
+hipError_t launch_pw_mid(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
+                         const float *opart, const float *ml, int nsplit, const float *feat_in, float *feat, void *q,
+                         void *k, void *v, float *vexp, hipStream_t s) {
     const int delay = g_diag_qkv_delay;  // tests only (pdsc_diag_qkv_delay): delay the split's K / V workgroups
+    const int B = plan.B, N = plan.N, Npad = plan.Npad;
     _Float16 *Q = static_cast<_Float16 *>(q), *K = static_cast<_Float16 *>(k), *V = static_cast<_Float16 *>(v);
-    if (use_pw2(B, Npad, f32)) {
-        const PwMsg m = msg3(lay.layer[layer], vfold);
-        const PwDense4 d = dense4(lay.layer[layer + 1], vfold);
-        const W2Sched S = sched_qkv(sched_msg(m, vfold), d, vfold);
-        with_bool(vfold, [&](auto vf) {
+    if (plan.pw2) {
+        const PwMsg m = msg3(lay.layer[layer], plan.vfold);
+        const PwDense4 d = dense4(lay.layer[layer + 1], plan.vfold);
+        const W2Sched S = sched_qkv(sched_msg(m, plan.vfold), d, plan.vfold);
+        with_bool(plan.vfold, [&](auto vf) {
             hipLaunchKernelGGL(pw2_mid_kernel<decltype(vf)::value>, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B),
                                dim3(PW2_W * 64), PW2_LDS, s, packed, S, m, d, opart, ml, nsplit, N, Npad, feat_in, feat, Q,
                                K, V, vexp);
         });
         return hipGetLastError();
     }
-    if (vfold) return hipErrorInvalidValue;  // the register-chained kernels only
-    if (!f32 && pw_waves8(B, Npad)) {
-        hipLaunchKernelGGL((pw_mid_kernel<32, false, 8>), dim3(Npad / 32, B, pw_qkv_split(B, Npad) ? 3 : 1), dim3(512),
+    if (plan.pw_mid8) {
+        hipLaunchKernelGGL((pw_mid_kernel<32, false, 8>), dim3(Npad / 32, B, plan.pw_mid_qkv3 ? 3 : 1), dim3(512),
                            pw_lds<32>(), s, packed,
                            msg3(lay.layer[layer]), dense4(lay.layer[layer + 1]), opart, ml, nsplit, N, Npad, feat_in,
-                           feat, Q, K, V, vexp, delay, (int)pw_prefetch_on());
+                           feat, Q, K, V, vexp, delay, (int)plan.pw_prefetch);
         return hipGetLastError();
     }
     PW_LAUNCH(pw_mid_kernel, Npad, packed, msg3(lay.layer[layer]), dense4(lay.layer[layer + 1]), opart, ml, nsplit,
@@ -2242,23 +2226,22 @@ hipError_t launch_pw_mid(const float *packed, const PackLayout &lay, int layer, 
     return hipGetLastError();
 }
 
-hipError_t launch_pw_last(const float *packed, const PackLayout &lay, bool f32, const float *opart,
-                          const float *ml, int nsplit, int B, int N, int Npad, const float *feat,
-                          float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
-                          bool vfold) {
-    if (use_pw2(B, Npad, f32)) {
-        const PwMsg m = msg3(lay.layer[lay.L - 1], vfold);
-        W2Sched S = sched_msg(m, vfold);
+hipError_t launch_pw_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *opart,
+                          const float *ml, int nsplit, const float *feat, float *feat_out, float *normed,
+                          _Float16 *normed_s, float *conf, hipStream_t s) {
+    const int B = plan.B, N = plan.N, Npad = plan.Npad;
+    if (plan.pw2) {
+        const PwMsg m = msg3(lay.layer[lay.L - 1], plan.vfold);
+        W2Sched S = sched_msg(m, plan.vfold);
         w2_sched_add(S, lay.c0, CH, CLS);
         w2_sched_add(S, lay.c2, CLS, CLS);
-        with_bool(vfold, [&](auto vf) {
+        with_bool(plan.vfold, [&](auto vf) {
             hipLaunchKernelGGL(pw2_last_kernel<decltype(vf)::value>, dim3((Npad + PW2_PTS - 1) / PW2_PTS, B),
                                dim3(PW2_W * 64), PW2_LDS, s, packed, S, m, lay.c0, lay.c2, lay.c4_w, lay.c4_b, opart, ml,
                                nsplit, N, Npad, feat, feat_out, normed, normed_s, conf);
         });
         return hipGetLastError();
     }
-    if (vfold) return hipErrorInvalidValue;  // the register-chained kernels only
     PW_LAUNCH(pw_last_kernel, N, packed, msg3(lay.layer[lay.L - 1]), lay.c0, lay.c2, lay.c4_w, lay.c4_b, opart, ml,
               nsplit, N, Npad, feat, feat_out, normed, normed_s, conf);
     return hipGetLastError();

@@ -15,6 +15,7 @@
 //   select_best  a10 first argmax of fitness, labels of the best hypothesis
 //   post_refine  a11 <= 20 device-side IRLS refits, one workgroup per pair
 #include "attention_h3.hpp"
+#include "launch_plan.hpp"
 
 namespace pdsc {
 
@@ -720,32 +721,11 @@ __global__ __launch_bounds__(256, R <= 80 ? 4 : 1) void knn_select_kernel(const 
     }
 }
 
-// Waves (= seeds) per workgroup of the one-wave-per-seed kernels (knn_select,
-// nsm_seed, kabsch_sums; none has a workgroup barrier): 4, unless that leaves
-// fewer than 2 workgroups per CU (a single N = 5000 pair has 500 seeds = 125
-// four-wave workgroups for 256 CUs), then 1 so the seeds spread over all CUs.
-static int seed_wpb(int B, int S) {
-    static const int force = [] {  // A/B knob PDSC_SEED_WPB=1|2|4 (measurement only)
-        const char *e = getenv("PDSC_SEED_WPB");
-        const int w = e ? atoi(e) : 0;
-        return (w == 1 || w == 2 || w == 4) ? w : 0;
-    }();
-    if (force) return force;
-    return (long)B * ((S + 3) / 4) < 512 ? 1 : 4;
-}
-
-hipError_t launch_knn_select(const float *dist, int B, int N, int S, int k, int *knn, hipStream_t s,
-                             Ragged rg) {
-    const int wpb = seed_wpb(B, S);
+hipError_t launch_knn_select(const TailPlan &tp, const float *dist, int B, int N, int S, int k, int *knn,
+                             hipStream_t s, Ragged rg) {
+    const int wpb = tp.wpb, bit = tp.knn_bitonic;
     const dim3 grid((S + wpb - 1) / wpb, B), block(64 * wpb);
     const int R = (N + 63) / 64;
-    // the fast path's <= 64 candidates ranked by a wave bitonic sort (128 x 1000:
-    // 36.5 vs 40.1 us per launch; 8 x 5000 and one pair equal); A/B knob
-    // PDSC_KNN_BITONIC=0: the readlane compare ranking (measurement only)
-    static const int bit = [] {
-        const char *e = getenv("PDSC_KNN_BITONIC");
-        return e ? atoi(e) : 1;
-    }();
     if (R <= 16)
         hipLaunchKernelGGL(knn_select_kernel<16>, grid, block, 0, s, dist, N, S, k, knn, rg, bit);
     else if (R <= 32)
@@ -1089,11 +1069,11 @@ size_t nsm_seed_lds_bytes(int k, int wpb) {
     return (size_t)wpb * (k * nsm_tstride(kc) + k * NSM_PSTR + 64) * sizeof(float);
 }
 
-hipError_t launch_nsm_seed(const void *feats, bool f32, const float *src, const float *tgt, const int *knn, int B,
-                           int N, int S, int k, int T, const float *sigma, const float *sigma_d, float *hist,
-                           unsigned *seed_flags, hipStream_t s, Ragged rg) {
+hipError_t launch_nsm_seed(const TailPlan &tp, const void *feats, bool f32, const float *src, const float *tgt,
+                           const int *knn, int B, int N, int S, int k, int T, const float *sigma, const float *sigma_d,
+                           float *hist, unsigned *seed_flags, hipStream_t s, Ragged rg) {
     if (k < 1 || k > KMAX) return hipErrorInvalidValue;
-    const int wpb = seed_wpb(B, S);
+    const int wpb = tp.wpb;
     const dim3 grid((S + wpb - 1) / wpb, B), block(64 * wpb);
     const size_t lds = nsm_seed_lds_bytes(k, wpb);
 #define NSM_LAUNCH(F, KC)                                                                                     \
@@ -1199,7 +1179,7 @@ PDSC_DEV void for_rows(const float *__restrict__ sb, const float *__restrict__ t
     }
 }
 
-// SOLVE (small batches, kabsch_small): lane 0 of the seed's wave also finishes
+// SOLVE (small batches, TailPlan::kabsch_fused): lane 0 of the seed's wave also finishes
 // the Kabsch solve (kabsch_finish on the same 15 sums kabsch_solve_kernel would
 // read back: the same bits) and writes trans -- one launch instead of two.
 // FIN (the testing forward): the seed's NSM weights are finished here, as
@@ -1364,28 +1344,16 @@ __global__ __launch_bounds__(256) void count_inliers_kernel(const float *__restr
     if (tid < ns) counts[(size_t)b * S + s0 + tid] = wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
 }
 
-// One solve per seed wave (kabsch_sums_kernel<true>) while the batch has at
-// most 1024 seeds (a single pair: 100); past that the solve kernel's 64 seeds
-// per wave keep the fp64 work off a lane-per-wave schedule.  A/B knob
-// PDSC_KABSCH_FUSED=0 (measurement only; the same bits either way).
-static bool kabsch_small(int n) {
-    static const bool off = [] {
-        const char *e = getenv("PDSC_KABSCH_FUSED");
-        return e && e[0] == '0';
-    }();
-    return !off && n <= 1024;
-}
-
-hipError_t launch_hypotheses(const float *src, const float *tgt, const int *knn, const float *weights,
-                             int B, int N, int S, int k, float tau, float *seed_trans, int *counts,
+hipError_t launch_hypotheses(const TailPlan &tp, const float *src, const float *tgt, const int *knn,
+                             const float *weights, int B, int N, int S, int k, float tau, float *seed_trans, int *counts,
                              float *sums, hipStream_t s, Ragged rg, const float *hist, const unsigned *seed_flags,
                              int T, float *wout) {
-    const int wpb = seed_wpb(B, S);
+    const int wpb = tp.wpb;
     const int n = B * S;
     const dim3 grid((S + wpb - 1) / wpb, B), block(64 * wpb);
     const bool fin = hist != nullptr;
     const float tau2 = sqrt_ge_threshold(tau);
-    if (kabsch_small(n)) {
+    if (tp.kabsch_fused) {
         // the inlier count in the same launch (count_inliers_kernel's integers)
         if (fin)
             hipLaunchKernelGGL((kabsch_sums_kernel<true, true, true>), grid, block, 0, s, src, tgt, knn, weights, N, S,

@@ -184,9 +184,11 @@ hipError_t launch_fold_vm(const float *w0, const float *b0, const float *wv, con
 // (h3_opart_off) for H3.
 // M's layouts: dense [B][N][N], symmetric-packed (mpack_*)
 enum MLayout { M_DENSE = 0, M_PACKED = 1 };
-// The attention launchers launch what the call's plan says (attention_plan.hpp:
-// plan_encoder, then plan.for_ragged(rg) for a ragged batch).
+// The encoder's and the tail's launchers launch what the call's plans say
+// (launch_plan.hpp: plan_encoder, then plan.for_ragged(rg) for a ragged batch;
+// plan_tail).
 struct EncoderPlan;
+struct TailPlan;
 // q, k, v: the fp16 hi/lo split layouts of attention_h3.hpp (4 B per element),
 // or fp32 [B][Npad][CH] rows for the exact-fp32 plan (attention.hpp).
 // M: dense [B][N][N] or symmetric-packed [B][mpack_floats(N)], per plan.m_layout.
@@ -214,15 +216,14 @@ hipError_t launch_split_qkv(const float *q, const float *k, const float *v, int 
 hipError_t launch_attn_combine(const float *opart, const float *ml, bool f32, int B, int N, int Npad,
                                int nsplit, float *msg, hipStream_t s);
 
-// Pointwise chains (one workgroup per PT points); q, k, v in launch_attention's layouts.
-// vfold (EncoderPlan::vfold; the register-chained kernels only): V is the folded
+// Pointwise chains (one workgroup per PT points) in the plan's form, over the
+// plan's B pairs; q, k, v in launch_attention's layouts.
+// plan.vfold (the register-chained kernels only): V is the folded
 // 64-channel V' in the first half of every V tile (the second half zero unless
 // fused, for attention_w64's 128-channel P.V), the partials' first 64 channels
 // are the folded O, and the message chain starts at fc0's BatchNorm / ReLU.
-// fused: the batch runs the fused plan (EncoderPlan::fused), whatever B this call covers.
-hipError_t launch_pw_first(const float *packed, const PackLayout &lay, const float *corr_pos, bool f32, int B,
-                           int N, int Npad, float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s,
-                           Ragged rg = {}, bool fused = false, bool vfold = false);
+hipError_t launch_pw_first(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *corr_pos,
+                           float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s, Ragged rg = {});
 // H3 split partials (nsplit) -> one combined split (opart1 [B][Npad][CH] in the
 // h3 tiling, ml1 = (0, 1)) that pw_mid / pw_last read with nsplit = 1 (small
 // batches: combine16's per-thread load chain is the pointwise launch's latency).
@@ -231,18 +232,18 @@ hipError_t launch_combine_rows(const float *opart, const float *ml, int B, int N
 // feat_in: the layer's rows (the residual); feat: where the new PointCN rows
 // go -- a different buffer (the Q / K / V workgroups of one point tile read
 // feat_in while one of them writes feat)
-hipError_t launch_pw_mid(const float *packed, const PackLayout &lay, int layer, bool f32, const float *opart,
-                         const float *ml, int nsplit, int B, int N, int Npad, const float *feat_in, float *feat,
-                         void *q, void *k, void *v, float *vexp, hipStream_t s, bool vfold = false);
-hipError_t launch_pw_last(const float *packed, const PackLayout &lay, bool f32, const float *opart,
-                          const float *ml, int nsplit, int B, int N, int Npad, const float *feat,
-                          float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
-                          bool vfold = false);
+hipError_t launch_pw_mid(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
+                         const float *opart, const float *ml, int nsplit, const float *feat_in, float *feat, void *q,
+                         void *k, void *v, float *vexp, hipStream_t s);
+hipError_t launch_pw_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *opart,
+                          const float *ml, int nsplit, const float *feat, float *feat_out, float *normed,
+                          _Float16 *normed_s, float *conf, hipStream_t s);
 
-hipError_t launch_local_max(const float *src, const float *conf, int B, int N, float radius,
+// The tail: tp = plan_tail(B, N, S) of the call's own B, N and S.
+hipError_t launch_local_max(const TailPlan &tp, const float *src, const float *conf, int B, int N, float radius,
                             float *lm, hipStream_t s, Ragged rg = {});
 // scratch: B S N words the ranking may use (the forward's kdist), or null
-hipError_t launch_seed_rank(const float *conf, const float *lm, int B, int N, int S, int *seeds,
+hipError_t launch_seed_rank(const TailPlan &tp, const float *conf, const float *lm, int B, int N, int S, int *seeds,
                             hipStream_t s, Ragged rg = {}, uint32_t *scratch = nullptr);
 
 // ns: normed as [B][N][2][128] fp16 hi/lo (qk_pos order, attention_h3.hpp)
@@ -252,21 +253,21 @@ hipError_t launch_split_rows(const float *x, size_t rows, _Float16 *out, hipStre
 // PDSC_PRECISION_F32 seed-row distances from the fp32 normed rows [B][N][128]
 hipError_t launch_knn_dist_f32(const float *normed, const int *seeds, int B, int N, int S, float *dist,
                                hipStream_t s, Ragged rg = {});
-hipError_t launch_knn_select(const float *dist, int B, int N, int S, int k, int *knn, hipStream_t s,
-                             Ragged rg = {});
+hipError_t launch_knn_select(const TailPlan &tp, const float *dist, int B, int N, int S, int k, int *knn,
+                             hipStream_t s, Ragged rg = {});
 // feats: the split normed copy [B][N][2][128] fp16 (as launch_knn_dist reads it),
 // or the fp32 normed rows [B][N][128] when f32
-hipError_t launch_nsm_seed(const void *feats, bool f32, const float *src, const float *tgt, const int *knn, int B,
-                           int N, int S, int k, int T, const float *sigma, const float *sigma_d, float *hist,
-                           unsigned *seed_flags, hipStream_t s, Ragged rg = {});
+hipError_t launch_nsm_seed(const TailPlan &tp, const void *feats, bool f32, const float *src, const float *tgt,
+                           const int *knn, int B, int N, int S, int k, int T, const float *sigma, const float *sigma_d,
+                           float *hist, unsigned *seed_flags, hipStream_t s, Ragged rg = {});
 hipError_t launch_nsm_finish(const float *hist, const unsigned *seed_flags, int B, int S, int k, int T, bool batch_global,
                              float *weights, int *iters_used, hipStream_t s, Ragged rg = {});
 // sums: scratch [B][S][15]
 // hist != NULL (the testing forward): the NSM weights are finished inside the
 // first launch (nsm_finish's arithmetic, per-pair allclose over hist /
 // seed_flags) and written to wout; `weights` is then not read.
-hipError_t launch_hypotheses(const float *src, const float *tgt, const int *knn, const float *weights,
-                             int B, int N, int S, int k, float tau, float *seed_trans, int *counts,
+hipError_t launch_hypotheses(const TailPlan &tp, const float *src, const float *tgt, const int *knn,
+                             const float *weights, int B, int N, int S, int k, float tau, float *seed_trans, int *counts,
                              float *sums, hipStream_t s, Ragged rg = {}, const float *hist = nullptr,
                              const unsigned *seed_flags = nullptr, int T = 0, float *wout = nullptr);
 // conf / range (both may be null): the forward's fp16 range guard -- a pair

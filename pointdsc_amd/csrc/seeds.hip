@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "launch_plan.hpp"
 #include "pdsc_internal.hpp"
 
 namespace pdsc {
@@ -540,68 +541,86 @@ __global__ __launch_bounds__(SORT_NT) void local_max_sort_kernel(const float *__
     lm[(size_t)b * Nstr + (int)(unsigned)skeys[q]] = viol ? 0.0f : 1.0f;
 }
 
-// The 16-row kernels below 1024 blocks of 64 rows (r04: 8 x 5000, 632 blocks:
-// seed_rank 49 vs 61 us at 4x the waves, local_max equal; 128 x 1000 keeps 64).
-// A/B knob PDSC_SEED_BLOCKS (measurement only) moves the bound.
-static bool seed_small(int B, int N) {
-    static const long lim = [] {
-        const char *e = getenv("PDSC_SEED_BLOCKS");
-        return e ? atol(e) : 1024L;
-    }();
-    return (long)B * ((N + 63) / 64) < lim;
-}
-
-// The sorted forms are opt-in (A/B knob PDSC_SEED_SORT=1, measurement only):
-// r04 measured them slower than the compare kernels at every bench shape --
-// 8 x 5000 forward 4.60 vs 4.51 ms, one N = 1000 pair 0.467 vs 0.441 ms, equal
-// at 128 x 1000 -- one 1024-thread workgroup per pair sorts 1024-8192 keys in
-// 55-91 barrier-separated steps, against the compare kernels' hundreds of
-// workgroups.
-static bool seed_sort_on() {
-    static const bool on = [] {
-        const char *e = getenv("PDSC_SEED_SORT");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
 static size_t sort_lds(int N) { return (size_t)std::max(64, 1 << (32 - __builtin_clz((unsigned)std::max(N - 1, 1)))) * 8; }
 
-// rows per thread of the NMS compare kernel: 2 (local_max_rows_kernel<16, 2>)
-// for batches on the 16-row blocks, else 1 (local_max_kernel) (r06: 8 x 5000
-// forward -15 / -24 us on two boxes and local_max 70.8 -> 60.3 us, but the
-// 64-row blocks slower with two rows -- 128 x 1000 31.4 -> 37.2 us, the ragged
-// bench 52 -> 72 us, r06j vs r06k profiles -- and one pair +2 us at N = 1000,
-// +5-10 us at N = 5000: profiles/r06_ab_lm*.log); A/B knob PDSC_LM_RPT=1|2|4
-// at every batch size (measurement only, the same bits)
-static int lm_rpt(int B, int N) {
-    static const int r = [] {
-        const char *e = getenv("PDSC_LM_RPT");
-        return e ? atoi(e) : 0;
-    }();
-    return r ? r : (B > 1 && seed_small(B, N) ? 2 : 1);
+// The tail's plan (launch_plan.hpp): every rule that picks a tail kernel and its
+// grid for a shape, each with the measurements behind it.
+TailPlan plan_tail(int B, int N, int S) {
+    const Knobs &k = knobs();
+    TailPlan t{};
+    // The 16-row kernels below 1024 blocks of 64 rows (r04: 8 x 5000, 632 blocks:
+    // seed_rank 49 vs 61 us at 4x the waves, local_max equal; 128 x 1000 keeps 64).
+    const bool small = (long)B * ((N + 63) / 64) < k.seed_blocks;
+    t.seed_rows = small ? 16 : 64;
+    // The sorted forms are opt-in (PDSC_SEED_SORT=1):
+    // r04 measured them slower than the compare kernels at every bench shape --
+    // 8 x 5000 forward 4.60 vs 4.51 ms, one N = 1000 pair 0.467 vs 0.441 ms, equal
+    // at 128 x 1000 -- one 1024-thread workgroup per pair sorts 1024-8192 keys in
+    // 55-91 barrier-separated steps, against the compare kernels' hundreds of
+    // workgroups.
+    // rows per thread of the NMS compare kernel: 2 (local_max_rows_kernel<16, 2>)
+    // for batches on the 16-row blocks, else 1 (local_max_kernel) (r06: 8 x 5000
+    // forward -15 / -24 us on two boxes and local_max 70.8 -> 60.3 us, but the
+    // 64-row blocks slower with two rows -- 128 x 1000 31.4 -> 37.2 us, the ragged
+    // bench 52 -> 72 us, r06j vs r06k profiles -- and one pair +2 us at N = 1000,
+    // +5-10 us at N = 5000: profiles/r06_ab_lm*.log); PDSC_LM_RPT=1|2|4: that many
+    // at every batch size (the same bits)
+    const int rpt = k.lm_rpt ? k.lm_rpt : (B > 1 && small ? 2 : 1);
+    t.nms_rpt = k.seed_sort && N <= NMS_SORT_MAX ? 0 : (rpt == 4 || rpt == 2) ? rpt : 1;
+    // The select form (seed_select_kernel) where the compare kernels' B N^2 work is
+    // large (>= 1e8 compares: 128 x 1000, 8 x 5000) and its keys and candidates fit
+    // the workgroup's LDS; split in two launches (seed_cand_rank_kernel: the A^2
+    // candidate compares over many workgroups) from S > 256 when the caller has
+    // scratch.  Measured (rocprofv3, one box): 128 x 1000 13.2 us vs 15.8 for the
+    // first select form (256 threads, every compare through an index) and ~26 for
+    // seed_rank_kernel<64>; one N = 1000 pair 9.5 vs 5.4 (seed_rank_kernel<16>).
+    const bool select = k.seed_select != 0 && sel_lds(N) <= 64 * 1024 &&
+                        (k.seed_select == 1 || (double)B * N * N >= 1e8);
+    if (select && !k.seed_sort)
+        t.rank = S > 256 && N >= 3 && k.sel_split ? RANK_SELECT_SPLIT : RANK_SELECT;
+    else
+        t.rank = k.seed_sort && N <= SORT_MAX ? RANK_SORT : RANK_COMPARE;
+    // Waves (= seeds) per workgroup of the one-wave-per-seed kernels (knn_select,
+    // nsm_seed, kabsch_sums; none has a workgroup barrier): 4, unless that leaves
+    // fewer than 2 workgroups per CU (a single N = 5000 pair has 500 seeds = 125
+    // four-wave workgroups for 256 CUs), then 1 so the seeds spread over all CUs.
+    t.wpb = k.seed_wpb ? k.seed_wpb : (long)B * ((S + 3) / 4) < 512 ? 1 : 4;
+    // the kNN fast path's <= 64 candidates ranked by a wave bitonic sort (128 x 1000:
+    // 36.5 vs 40.1 us per launch; 8 x 5000 and one pair equal)
+    t.knn_bitonic = k.knn_bitonic;
+    // One solve per seed wave (kabsch_sums_kernel<true>) while the batch has at
+    // most 1024 seeds (a single pair: 100); past that the solve kernel's 64 seeds
+    // per wave keep the fp64 work off a lane-per-wave schedule.
+    t.kabsch_fused = k.kabsch_fused && B * S <= 1024;
+    // The testing forward's fused tail launches (nsm_finish inside the hypotheses'
+    // first launch, select_best + post_refine in one): the same bits, two launches
+    // fewer per forward.
+    t.tail_fused = k.tail_fused;
+    return t;
 }
 
-hipError_t launch_local_max(const float *src, const float *conf, int B, int N, float radius,
+hipError_t launch_local_max(const TailPlan &tp, const float *src, const float *conf, int B, int N, float radius,
                             float *lm, hipStream_t s, Ragged rg) {
-    if (seed_sort_on() && N <= NMS_SORT_MAX) {
+    const bool small = tp.seed_rows == 16;
+    if (tp.nms_rpt == 0) {
         const size_t lds = sort_lds(N) + (size_t)N * sizeof(f32x4);
         hipLaunchKernelGGL(local_max_sort_kernel, dim3((N + SORT_NT - 1) / SORT_NT, B), dim3(SORT_NT), lds, s, src, conf,
                            N, sqrt_ge_threshold(radius), lm, rg);
-    } else if (lm_rpt(B, N) == 4) {
-        if (seed_small(B, N))
+    } else if (tp.nms_rpt == 4) {
+        if (small)
             hipLaunchKernelGGL((local_max_rows_kernel<16, 4>), dim3((N + 63) / 64, B), dim3(256), 0, s, src, conf, N,
                                sqrt_ge_threshold(radius), lm, rg);
         else
             hipLaunchKernelGGL((local_max_rows_kernel<64, 4>), dim3((N + 255) / 256, B), dim3(256), 0, s, src, conf,
                                N, sqrt_ge_threshold(radius), lm, rg);
-    } else if (lm_rpt(B, N) == 2) {
-        if (seed_small(B, N))
+    } else if (tp.nms_rpt == 2) {
+        if (small)
             hipLaunchKernelGGL((local_max_rows_kernel<16, 2>), dim3((N + 31) / 32, B), dim3(256), 0, s, src, conf, N,
                                sqrt_ge_threshold(radius), lm, rg);
         else
             hipLaunchKernelGGL((local_max_rows_kernel<64, 2>), dim3((N + 127) / 128, B), dim3(256), 0, s, src, conf,
                                N, sqrt_ge_threshold(radius), lm, rg);
-    } else if (seed_small(B, N))
+    } else if (small)
         hipLaunchKernelGGL(local_max_kernel<16>, dim3((N + 15) / 16, B), dim3(256), 0, s, src, conf, N,
                            sqrt_ge_threshold(radius), lm, rg);
     else
@@ -610,43 +629,19 @@ hipError_t launch_local_max(const float *src, const float *conf, int B, int N, f
     return hipGetLastError();
 }
 
-// The select form (seed_select_kernel) where the compare kernels' B N^2 work is
-// large (>= 1e8 compares: 128 x 1000, 8 x 5000) and its keys and candidates fit
-// the workgroup's LDS; split in two launches (seed_cand_rank_kernel: the A^2
-// candidate compares over many workgroups) from S > 256 when the caller has
-// scratch.  Measured (rocprofv3, one box): 128 x 1000 13.2 us vs 15.8 for the
-// first select form (256 threads, every compare through an index) and ~26 for
-// seed_rank_kernel<64>; one N = 1000 pair 9.5 vs 5.4 (seed_rank_kernel<16>).
-// A/B knob PDSC_SEED_SELECT (measurement only): 0 never, 1 at every batch size.
-static bool seed_select_on(int B, int N) {
-    static const int mode = [] {
-        const char *e = getenv("PDSC_SEED_SELECT");
-        return e ? atoi(e) : 2;
-    }();
-    if (mode == 0 || sel_lds(N) > 64 * 1024) return false;
-    return mode == 1 || (double)B * N * N >= 1e8;
-}
-
-hipError_t launch_seed_rank(const float *conf, const float *lm, int B, int N, int S, int *seeds,
+hipError_t launch_seed_rank(const TailPlan &tp, const float *conf, const float *lm, int B, int N, int S, int *seeds,
                             hipStream_t s, Ragged rg, uint32_t *scratch) {
-    if (seed_select_on(B, N) && !seed_sort_on()) {
-        // scratch per pair: 2 S + 1 <= S N words
-        static const bool split_off = [] {  // A/B knob PDSC_SEL_SPLIT=0 (measurement only)
-            const char *e = getenv("PDSC_SEL_SPLIT");
-            return e && e[0] == '0';
-        }();
-        if (scratch && S > 256 && N >= 3 && !split_off) {
-            hipLaunchKernelGGL(seed_select_kernel<true>, dim3(B), dim3(SEL_NT), sel_lds(N), s, conf, lm, N, S, seeds,
-                               scratch, rg);
-            hipLaunchKernelGGL(seed_cand_rank_kernel, dim3(SEL_CMAX / SEL_RQ, B), dim3(256), 0, s, scratch, N, S,
-                               seeds, rg);
-        } else {
-            hipLaunchKernelGGL(seed_select_kernel<false>, dim3(B), dim3(SEL_NT), sel_lds(N), s, conf, lm, N, S, seeds,
-                               nullptr, rg);
-        }
-    } else if (seed_sort_on() && N <= SORT_MAX)
+    if (tp.rank == RANK_SELECT_SPLIT && scratch) {  // scratch per pair: 2 S + 1 <= S N words
+        hipLaunchKernelGGL(seed_select_kernel<true>, dim3(B), dim3(SEL_NT), sel_lds(N), s, conf, lm, N, S, seeds,
+                           scratch, rg);
+        hipLaunchKernelGGL(seed_cand_rank_kernel, dim3(SEL_CMAX / SEL_RQ, B), dim3(256), 0, s, scratch, N, S, seeds,
+                           rg);
+    } else if (tp.rank == RANK_SELECT_SPLIT || tp.rank == RANK_SELECT)
+        hipLaunchKernelGGL(seed_select_kernel<false>, dim3(B), dim3(SEL_NT), sel_lds(N), s, conf, lm, N, S, seeds,
+                           nullptr, rg);
+    else if (tp.rank == RANK_SORT)
         hipLaunchKernelGGL(seed_rank_sort_kernel, dim3(B), dim3(SORT_NT), sort_lds(N), s, conf, lm, N, S, seeds, rg);
-    else if (seed_small(B, N))
+    else if (tp.seed_rows == 16)
         hipLaunchKernelGGL(seed_rank_kernel<16>, dim3((N + 15) / 16, B), dim3(256), 0, s, conf, lm, N, S, seeds, rg);
     else
         hipLaunchKernelGGL(seed_rank_kernel<64>, dim3((N + 63) / 64, B), dim3(256), 0, s, conf, lm, N, S, seeds, rg);
