@@ -541,6 +541,108 @@ int32_t pdsc_ransac_correspondence(const float *src, const float *tgt, int32_t N
                                    const pdsc_ransac_debug *debug /* HOST struct of device pointers, may be NULL */,
                                    void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
 
+/* ------------------------------------------ f7 filtered RANSAC front end ---
+ * The filter stage of the fork's "fast RANSAC" pipeline (algorithms/FR.py:36-58
+ * and :101-114 on algorithms/matching.py; test.py:163-170, --algo RANSAC --mode
+ * no_filter | MFR | GPF) between descriptor matching and f6.  Nothing here
+ * synchronises the stream, counts stay in device memory, every argument is
+ * checked on the host before any device work (PDSC_ERR_ARG: sizes below their
+ * minimum, null pointers, a workspace that is too small, a factor or radius
+ * that is negative or not finite; PDSC_ERR_UNSUPPORTED: D > 64, grid_wid >
+ * 64, more than 262144 rows in pdsc_gpf_select).  Two calls are bitwise equal (integer atomics only).
+ *
+ * pdsc_nn2 (matching.py:22-65 find_nn(return_2nd=True), and the reverse
+ * find_nn inside nn_to_mutual :225-229).  f0 [N0,D], f1 [N1,D] fp32, 1 <= D <=
+ * 64, N0 >= 1, N1 >= 2.  All in fp32, no contraction except the fmaf named:
+ *   dot(a, b) = fmaf(a_k, b_k, acc) for k = 0 .. D-1 ascending, acc = 0 first;
+ *   dist2(i, j) = (dot(f0_i, f0_i) + dot(f1_j, f1_j)) - 2 * dot(f0_i, f1_j);
+ *   dist(i, j)  = sqrt(dist2 < 1e-30 ? 1e-30 : dist2)    (clamp_min: NaN stays);
+ *   nn1[i] = argmin_j, nn2[i] = argmin_{j != nn1[i]}, rev[j] = argmin_i of the
+ *   same values (each is computed once, both directions see the same bits), all
+ *   under the order (dist, index): ties go to the lower index in both
+ *   directions (torch.min leaves that open); a NaN distance orders before
+ *   every number (numpy.argmin's rule, as pdsc_mutual_nn).
+ * The N0 x N1 matrix is never stored.  The column tiles of a row stripe may be
+ * split over several workgroups whose (dist, index) pairs are merged exactly;
+ * the result does not depend on the split.  pdsc_nn2_split is pdsc_nn2 with
+ * the split given (>= 1, clamped to the column tiles and to 16): a debug entry
+ * point for tests, same workspace.
+ *
+ * pdsc_match_ratio (matching.py:89-98 calc_distance_ratio_in_feature_space,
+ * :210-223 mark_best_buddies, :122-137 normalize and the best-buddy offset):
+ *   norm2(a, b) = fmaf(d_k, d_k, acc), d_k = a_k - b_k, k ascending;
+ *   feat_dist[i] = sqrt(norm2(f0_i, f1_nn1[i])) / (sqrt(norm2(f0_i, f1_nn2[i])) + 1e-6)
+ *   (computed directly as the reference does, not from dist above);
+ *   is_bb[i] = (rev[nn1[i]] == i); the rows with is_bb in ascending i are the
+ *   MFR output (nn_to_mutual); num_bb = their number (device int32);
+ *   norm[i] = (feat_dist[i] - min) / (max - min) over all rows, minus 1 where
+ *   is_bb.  Deviation: with max == min the reference divides by zero; here the
+ *   quotient is defined as 0 (so norm is -1 on best buddies, 0 elsewhere).
+ *   An index outside [0, N1) gives feat_dist NaN and is_bb 0 (nothing is read).
+ * rev == NULL: only feat_dist is written (is_bb, norm, num_bb may be NULL).
+ *
+ * pdsc_gpf_select (matching.py:100-208 Grid_Prioritized_Filter, BB_first=False;
+ * BB_first=True has no caller in the reference and is not built).  xyz0 [N0,3]
+ * are the source points of rows 0 .. N0-1, norm [N0] and num_bb as above.
+ *   Cells     to_quads (:139-145) bit-exactly in fp32, in its operation order:
+ *             q(X) = floor(G * ((X - m) / ((M - m) + 1e-3f))) with m, M the
+ *             minimum and maximum of the column, for x and for y; cell = q(x) G
+ *             + q(y).  A row with q outside [0, G) (M - m so large that the
+ *             1e-3 is lost) is in no cell, as in the reference's loops, and is
+ *             never kept; its debug cell is -1.  1 <= G = grid_wid <= 64.
+ *   Heights   max_per_quad = integer rows per cell; TOTAL = gpf_factor * num_bb
+ *             in fp64; the bisection of :163-180 as written (|max - min| > 2,
+ *             the three-way compare) in fp64; per_quad = min(max_per_quad,
+ *             rint(height)): np.round is round half to even.  Deviation: each
+ *             step's sum over the cells is taken sequentially in cell order,
+ *             where the reference's per_quad.sum() is numpy's blocked pairwise
+ *             summation.  Counts and heights that are dyadic (TOTAL an integer
+ *             or a half) sum exactly either way; for another gpf_factor *
+ *             num_bb the two sums can differ in the last place and a step's
+ *             == / < / > can then fall the other way.
+ *   Selection a cell with per_quad == max_per_quad keeps every row; another
+ *             keeps the int(per_quad) rows that are lowest under (norm, row):
+ *             ties to the lower row (the reference's argsort is unstable).
+ *   Cost      the rows of a truncated cell are ranked by counting inside the
+ *             cell: n^2 word compares for a cell of n rows, N0^2 when one cell
+ *             holds every row (G = 1, or one far outlier stretching the
+ *             extent).  N0 is therefore limited to 262144 (PDSC_ERR_UNSUPPORTED
+ *             above; the reference's clouds are a few ten thousand keypoints).
+ *   Output    kept [N0 capacity]: the kept rows ascending; *count (device
+ *             int32); kept_norm [N0 capacity] = norm of those rows (may be NULL).
+ * pdsc_gpf_debug: any member may be NULL.
+ *
+ * pdsc_refit_inliers (FR.py:101-114): the inliers of pose (device double[16],
+ * row-major 4x4) among the N pairs src[i], tgt[i] are the rows with |R s + t -
+ * tgt|^2 < radius^2 in fp64 (f6's Score); trans = one unit-weight fp64 Kabsch
+ * over them -- the same code as f6's refit, so on f6's own point set and pose
+ * the two are bitwise equal.  FR calls it on the unfiltered pairs.  With fewer
+ * than 3 inliers the reference's estimate is undefined: trans is then the
+ * input pose, bit for bit.  *count (device int32, may be NULL) = the inliers
+ * of the INPUT pose, labels [N] (may be NULL) mark them; trans_f32 = (float)
+ * trans (may be NULL).  trans may alias pose.                                 */
+typedef struct pdsc_gpf_debug {       /* HOST struct of device pointers */
+    int32_t *cell;                    /* [N0] */
+    int32_t *max_per_quad;            /* [G*G] */
+    double  *per_quad;                /* [G*G] */
+    double  *height;                  /* [1] the bisection's final height, before rint */
+} pdsc_gpf_debug;
+size_t  pdsc_nn2_workspace_bytes(int32_t N0, int32_t N1);
+int32_t pdsc_nn2(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int32_t *nn1, int32_t *nn2,
+                 int32_t *rev /* [N1] */, void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+int32_t pdsc_nn2_split(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int32_t split,
+                       int32_t *nn1, int32_t *nn2, int32_t *rev, void *workspace, size_t workspace_bytes,
+                       pdsc_stream_t stream);
+int32_t pdsc_match_ratio(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, const int32_t *nn1,
+                         const int32_t *nn2, const int32_t *rev, int32_t *is_bb, float *feat_dist, float *norm,
+                         int32_t *num_bb, pdsc_stream_t stream);
+size_t  pdsc_gpf_select_workspace_bytes(int32_t N0, int32_t grid_wid);
+int32_t pdsc_gpf_select(const float *xyz0, const float *norm, const int32_t *num_bb, int32_t N0, int32_t grid_wid,
+                        double gpf_factor, int32_t *kept, int32_t *count, float *kept_norm,
+                        const pdsc_gpf_debug *debug, void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+int32_t pdsc_refit_inliers(const double *pose, const float *src, const float *tgt, int32_t N, double radius,
+                           double *trans, float *trans_f32, int32_t *count, float *labels, pdsc_stream_t stream);
+
 /* ----------------------------------------------- full testing forward ------
  * PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197)
  * for B independent pairs: compat -> encoder -> classifier -> seeds -> kNN ->

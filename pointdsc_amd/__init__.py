@@ -4,17 +4,28 @@
 ``models.PointDSC.PointDSC``; ``pointdsc_amd.kernels`` exposes each hot-path op;
 ``pointdsc_amd.icp`` refines a pose by point-to-point ICP (the drivers' "+ICP"
 row); ``pointdsc_amd.ransac`` is RANSAC on correspondences (the drivers' RANSAC
-baseline and ``--solver RANSAC``); the C ABI is ``include/pdsc.h`` /
+baseline and ``--solver RANSAC``); ``pointdsc_amd.matching`` / ``pointdsc_amd.fr``
+are the fork's correspondence filters (MFR, GPF) and its filtered RANSAC ``FR``;
+the C ABI is ``include/pdsc.h`` /
 ``pointdsc_amd/libpdsc.so``.
 """
 __version__ = "0.1.0"
 
 _ICP = ("icp_refine", "registration_icp")
 _RANSAC = ("registration_ransac_based_on_correspondence", "ransac_solver")
-__all__ = [*_ICP, *_RANSAC]
+_MATCHING = ("find_nn", "find_2nn", "nn_to_mutual", "mark_best_buddies", "calc_distance_ratio_in_feature_space",
+             "Grid_Prioritized_Filter", "measure_inlier_ratio", "refit_inliers")
+_FR = ("FR",)
+__all__ = [*_ICP, *_RANSAC, *_MATCHING, *_FR]
 
 
-def __getattr__(name):  # the ICP / RANSAC entry points, without importing torch on `import pointdsc_amd`
+def __getattr__(name):  # the ICP / RANSAC / FR entry points, without importing torch on `import pointdsc_amd`
+    if name in _MATCHING:
+        from . import matching
+        return getattr(matching, name)
+    if name in _FR:
+        from . import fr
+        return getattr(fr, name)
     if name in _ICP:
         from . import icp
         return getattr(icp, name)

@@ -60,6 +60,11 @@ class PdscRansacDebug(ctypes.Structure):
     _fields_ = [("samples", vp), ("count", vp), ("sumsq", vp), ("trans", vp)]
 
 
+class PdscGpfDebug(ctypes.Structure):
+    """``struct pdsc_gpf_debug`` (include/pdsc.h): optional outputs of pdsc_gpf_select."""
+    _fields_ = [("cell", vp), ("max_per_quad", vp), ("per_quad", vp), ("height", vp)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "pdsc_version": (ctypes.c_char_p, []),
@@ -128,6 +133,14 @@ _PROTOS = {
     "pdsc_ransac_correspondence": (c_int32, [vp, vp, c_int32, c_double, c_int32, c_double, c_int32, c_double,
                                              ctypes.c_uint64, c_int32, vp, vp, vp, ctypes.POINTER(PdscRansacDebug),
                                              vp, c_size_t, vp]),
+    "pdsc_nn2_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "pdsc_nn2": (c_int32, [vp, vp, c_int32, c_int32, c_int32, vp, vp, vp, vp, c_size_t, vp]),
+    "pdsc_nn2_split": (c_int32, [vp, vp, c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, c_size_t, vp]),
+    "pdsc_match_ratio": (c_int32, [vp, vp, c_int32, c_int32, c_int32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pdsc_gpf_select_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "pdsc_gpf_select": (c_int32, [vp, vp, vp, c_int32, c_int32, c_double, vp, vp, vp, ctypes.POINTER(PdscGpfDebug),
+                                  vp, c_size_t, vp]),
+    "pdsc_refit_inliers": (c_int32, [vp, vp, vp, c_int32, c_double, vp, vp, vp, vp, vp]),
     "pdsc_forward_training_workspace_bytes": (c_size_t, [CFG, c_int32, c_int32]),
     "pdsc_range_status": (c_int32, [vp, c_int32, ctypes.POINTER(c_int32), vp]),
     "pdsc_range_poll": (c_int32, [vp, c_int32, vp]),

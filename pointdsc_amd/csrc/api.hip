@@ -1248,6 +1248,73 @@ int32_t pdsc_ransac_correspondence(const float *src, const float *tgt, int32_t N
     return PDSC_OK;
 }
 
+// ------------------------------------------------ f7 filtered RANSAC front end
+size_t pdsc_nn2_workspace_bytes(int32_t N0, int32_t N1) { return N0 < 1 || N1 < 2 ? 0 : nn2_workspace_bytes(N0, N1); }
+
+static int32_t check_desc_args(int32_t N0, int32_t N1, int32_t D) {
+    if (N0 < 1 || N1 < 2 || D < 1) return fail(PDSC_ERR_ARG, "N0=%d N1=%d D=%d (need N0 >= 1, N1 >= 2, D >= 1)", N0, N1, D);
+    if (D > 64) return fail(PDSC_ERR_UNSUPPORTED, "D=%d > 64", D);
+    return PDSC_OK;
+}
+
+static int32_t nn2_call(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int split, int32_t *nn1,
+                        int32_t *nn2, int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_desc_args(N0, N1, D));
+    if (!f0 || !f1 || !nn1 || !nn2 || !rev || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_nn2_workspace_bytes(N0, N1)));
+    HIPCHK(launch_nn2(f0, f1, N0, N1, D, split, nn1, nn2, rev, ws, S_(stream)));
+    return PDSC_OK;
+}
+
+int32_t pdsc_nn2(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int32_t *nn1, int32_t *nn2,
+                 int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    return nn2_call(f0, f1, N0, N1, D, 0, nn1, nn2, rev, ws, ws_bytes, stream);
+}
+
+int32_t pdsc_nn2_split(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int32_t split,
+                       int32_t *nn1, int32_t *nn2, int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    if (split < 1) return fail(PDSC_ERR_ARG, "split=%d (need >= 1)", split);
+    return nn2_call(f0, f1, N0, N1, D, split, nn1, nn2, rev, ws, ws_bytes, stream);
+}
+
+int32_t pdsc_match_ratio(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, const int32_t *nn1,
+                         const int32_t *nn2, const int32_t *rev, int32_t *is_bb, float *feat_dist, float *norm,
+                         int32_t *num_bb, pdsc_stream_t stream) {
+    RET_IF(check_desc_args(N0, N1, D));
+    if (!f0 || !f1 || !nn1 || !nn2 || !feat_dist) return fail(PDSC_ERR_ARG, "null pointer");
+    if (rev && (!is_bb || !norm || !num_bb)) return fail(PDSC_ERR_ARG, "null pointer (is_bb, norm, num_bb go with rev)");
+    HIPCHK(launch_match_ratio(f0, f1, N0, N1, D, nn1, nn2, rev, is_bb, feat_dist, norm, num_bb, S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_gpf_select_workspace_bytes(int32_t N0, int32_t grid_wid) {
+    return N0 < 1 || N0 > GPF_MAX_ROWS || grid_wid < 1 || grid_wid > 64 ? 0 : gpf_workspace_bytes(N0, grid_wid);
+}
+
+int32_t pdsc_gpf_select(const float *xyz0, const float *norm, const int32_t *num_bb, int32_t N0, int32_t grid_wid,
+                        double gpf_factor, int32_t *kept, int32_t *count, float *kept_norm,
+                        const pdsc_gpf_debug *debug, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    if (N0 < 1 || grid_wid < 1) return fail(PDSC_ERR_ARG, "N0=%d grid_wid=%d (need >= 1)", N0, grid_wid);
+    if (grid_wid > 64) return fail(PDSC_ERR_UNSUPPORTED, "grid_wid=%d > 64", grid_wid);
+    if (N0 > GPF_MAX_ROWS) return fail(PDSC_ERR_UNSUPPORTED, "N0=%d > %d (rank counting inside a cell)", N0, GPF_MAX_ROWS);
+    if (!(gpf_factor >= 0.0) || !std::isfinite(gpf_factor))
+        return fail(PDSC_ERR_ARG, "gpf_factor %g must be >= 0 and finite", gpf_factor);
+    if (!xyz0 || !norm || !num_bb || !kept || !count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_gpf_select_workspace_bytes(N0, grid_wid)));
+    HIPCHK(launch_gpf_select(xyz0, norm, num_bb, N0, grid_wid, gpf_factor, kept, count, kept_norm, debug, ws,
+                             S_(stream)));
+    return PDSC_OK;
+}
+
+int32_t pdsc_refit_inliers(const double *pose, const float *src, const float *tgt, int32_t N, double radius,
+                           double *trans, float *trans_f32, int32_t *count, float *labels, pdsc_stream_t stream) {
+    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
+    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(PDSC_ERR_ARG, "radius %g must be > 0 and finite", radius);
+    if (!pose || !src || !tgt || !trans) return fail(PDSC_ERR_ARG, "null pointer");
+    HIPCHK(launch_refit_inliers(pose, src, tgt, N, radius, trans, trans_f32, count, labels, S_(stream)));
+    return PDSC_OK;
+}
+
 // ------------------------------------------------- f1 correspondence construction
 size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
     return align_bytes((size_t)Ns * 8) + align_bytes((size_t)Nt * 8);

@@ -21,21 +21,6 @@ namespace pdsc {
 constexpr int NN_T = 64;     // tile edge
 constexpr int NN_DMAX = 64;  // descriptor width limit (FCGF 32, FPFH 33)
 
-// order-preserving float -> uint; NaN -> 0 (numpy.argmin returns the first NaN)
-PDSC_DEV uint32_t nn_key(float f) {
-    if (f != f) return 0u;
-    if (f == 0.0f) f = 0.0f;
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-PDSC_DEV unsigned long long umin64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-
-PDSC_DEV unsigned long long shfl_xor64(unsigned long long v, int m) {
-    const int lo = __shfl_xor((int)(uint32_t)v, m), hi = __shfl_xor((int)(uint32_t)(v >> 32), m);
-    return ((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo;
-}
-
 __global__ __launch_bounds__(256) void nn_argmin_kernel(const float *__restrict__ A, const float *__restrict__ Bd,
                                                         int Na, int Nb, int D, unsigned long long *__restrict__ rowkey,
                                                         unsigned long long *__restrict__ colkey) {

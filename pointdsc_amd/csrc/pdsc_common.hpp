@@ -244,4 +244,20 @@ PDSC_DEV void kabsch_rotation(const double H[9], double R[9]) {
     R[8] = v0.z * u0.z + v1.z * u1.z + d * v2.z * u2.z;
 }
 
+// ---- (key, index) words of the nearest-neighbour kernels (corr.hip, match_filter.hip)
+// order-preserving float -> uint; NaN -> 0 (numpy.argmin returns the first NaN)
+PDSC_DEV uint32_t nn_key(float f) {
+    if (f != f) return 0u;
+    if (f == 0.0f) f = 0.0f;
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+PDSC_DEV unsigned long long umin64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+PDSC_DEV unsigned long long shfl_xor64(unsigned long long v, int m) {
+    const int lo = __shfl_xor((int)(uint32_t)v, m), hi = __shfl_xor((int)(uint32_t)(v >> 32), m);
+    return ((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
 }  // namespace pdsc

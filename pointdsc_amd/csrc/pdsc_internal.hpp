@@ -338,6 +338,28 @@ hipError_t launch_ransac(const float *src, const float *tgt, int N, double max_d
                          int H, double confidence, unsigned long long seed, int refit, float *trans_f32, float *labels,
                          pdsc_ransac_result *res, const pdsc_ransac_debug *debug, void *ws, hipStream_t s);
 
+// the refit over a point set of the caller's (ransac.hip: shares the finish kernel's scoring and Kabsch)
+hipError_t launch_refit_inliers(const double *pose, const float *src, const float *tgt, int N, double radius,
+                                double *trans, float *trans_f32, int *count, float *labels, hipStream_t s);
+
+// filtered-RANSAC front end (match_filter.hip, f7)
+constexpr int NN2_MAX_SPLIT = 16;  // column splits per row stripe the workspace is sized for
+int nn2_default_split(int Na, int Nb);
+size_t nn2_workspace_bytes(int Na, int Nb);
+// split: column splits per row stripe, 0 = nn2_default_split (clamped to the column tiles and NN2_MAX_SPLIT)
+hipError_t launch_nn2(const float *A, const float *B, int Na, int Nb, int D, int split, int *nn1, int *nn2, int *rev,
+                      void *ws, hipStream_t s);
+// rev == nullptr: only feat_dist
+hipError_t launch_match_ratio(const float *f0, const float *f1, int N0, int N1, int D, const int *nn1, const int *nn2,
+                              const int *rev, int *is_bb, float *feat_dist, float *norm, int *num_bb, hipStream_t s);
+// Rows pdsc_gpf_select accepts: a truncated cell of n rows costs n^2 word compares (gpf_rank_kernel), so one
+// cell holding every row costs N0^2 -- 6.9e10 at this limit, well under a second on 256 CUs.
+constexpr int GPF_MAX_ROWS = 1 << 18;
+size_t gpf_workspace_bytes(int N0, int G);
+hipError_t launch_gpf_select(const float *xyz0, const float *norm, const int *num_bb, int N0, int G, double factor,
+                             int *kept, int *count, float *kept_norm, const pdsc_gpf_debug *debug, void *ws,
+                             hipStream_t s);
+
 // correspondence construction (corr.hip)
 #define HIP_RET(expr)                        \
     do {                                      \

@@ -549,6 +549,44 @@ PDSC_DEV double block_sum(double v, double *red, int tid) {
     return s;
 }
 
+// The refit (algorithms/FR.py:101-114): one unit-weight fp64 Kabsch over the
+// rows with d^2 < r2 under c, centred, in a fixed order; c <- the new pose, the
+// same bits in every thread.  n: the inlier count (already summed over the
+// workgroup), sa / sb: this thread's partial coordinate sums over its inliers.
+PDSC_DEV void refit_kabsch(const float *__restrict__ src, const float *__restrict__ tgt, int N, double r2, double n,
+                           double sa[3], double sb[3], double c[12], double *red, int tid) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        sa[k] = block_sum(sa[k], red, tid);
+        sb[k] = block_sum(sb[k], red, tid);
+    }
+    const double inv = 1.0 / n;
+    const D3 ca = d3(sa[0] * inv, sa[1] * inv, sa[2] * inv), cb = d3(sb[0] * inv, sb[1] * inv, sb[2] * inv);
+    double Hm[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Hm[k] = 0.0;
+    for (int i = tid; i < N; i += RANSAC_FIN) {
+        const D3 a0 = load3(src, i), b0 = load3(tgt, i);
+        if (ransac_d2(c, a0.x, a0.y, a0.z, b0.x, b0.y, b0.z) < r2) {
+            const D3 a = sub3(a0, ca), b = sub3(b0, cb);
+            Hm[0] += a.x * b.x;
+            Hm[1] += a.x * b.y;
+            Hm[2] += a.x * b.z;
+            Hm[3] += a.y * b.x;
+            Hm[4] += a.y * b.y;
+            Hm[5] += a.y * b.z;
+            Hm[6] += a.z * b.x;
+            Hm[7] += a.z * b.y;
+            Hm[8] += a.z * b.z;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Hm[k] = block_sum(Hm[k], red, tid);
+    double Rf[9];
+    kabsch_rotation_svd(Hm, Rf);
+    kabsch_pose(Rf, ca, cb, c);  // every thread: the same bits
+}
+
 __global__ __launch_bounds__(RANSAC_FIN) void ransac_finish_kernel(const float *__restrict__ src,
                                                                    const float *__restrict__ tgt, int N, double r2,
                                                                    int refit, const RansacState *st, float *trans_f32,
@@ -573,36 +611,7 @@ __global__ __launch_bounds__(RANSAC_FIN) void ransac_finish_kernel(const float *
     }
     if (refit_now) {
         n = block_sum(n, red, tid);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            sa[k] = block_sum(sa[k], red, tid);
-            sb[k] = block_sum(sb[k], red, tid);
-        }
-        const double inv = 1.0 / n;
-        const D3 ca = d3(sa[0] * inv, sa[1] * inv, sa[2] * inv), cb = d3(sb[0] * inv, sb[1] * inv, sb[2] * inv);
-        double Hm[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Hm[k] = 0.0;
-        for (int i = tid; i < N; i += RANSAC_FIN) {
-            const D3 a0 = load3(src, i), b0 = load3(tgt, i);
-            if (ransac_d2(c, a0.x, a0.y, a0.z, b0.x, b0.y, b0.z) < r2) {
-                const D3 a = sub3(a0, ca), b = sub3(b0, cb);
-                Hm[0] += a.x * b.x;
-                Hm[1] += a.x * b.y;
-                Hm[2] += a.x * b.z;
-                Hm[3] += a.y * b.x;
-                Hm[4] += a.y * b.y;
-                Hm[5] += a.y * b.z;
-                Hm[6] += a.z * b.x;
-                Hm[7] += a.z * b.y;
-                Hm[8] += a.z * b.z;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Hm[k] = block_sum(Hm[k], red, tid);
-        double Rf[9];
-        kabsch_rotation_svd(Hm, Rf);
-        kabsch_pose(Rf, ca, cb, c);  // every thread: the same bits
+        refit_kabsch(src, tgt, N, r2, n, sa, sb, c, red, tid);
     }
     if (tid != 0) return;
     double T[16];
@@ -621,6 +630,55 @@ __global__ __launch_bounds__(RANSAC_FIN) void ransac_finish_kernel(const float *
     }
     if (trans_f32)
         for (int i = 0; i < 16; ++i) trans_f32[i] = (float)T[i];
+}
+
+// ---------------------------------------------------------------- refit_inliers
+// pdsc_refit_inliers (f7): ransac_finish_kernel's refit over a point set of the
+// caller's choice under a pose of the caller's (FR.py:101-114 refits over the
+// unfiltered pairs, RANSAC scored the filtered ones).  With fewer than 3 inliers
+// the pose is returned unchanged.
+__global__ __launch_bounds__(RANSAC_FIN) void refit_inliers_kernel(const double *pose,  // trans may alias it
+                                                                   const float *__restrict__ src,
+                                                                   const float *__restrict__ tgt, int N, double r2,
+                                                                   double *trans, float *trans_f32, int *count,
+                                                                   float *labels) {
+    __shared__ double red[RANSAC_FIN / 64];
+    const int tid = threadIdx.x;
+    double T[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) T[k] = pose[k];
+    double c[12] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10], T[3], T[7], T[11]};
+    double n = 0.0, sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0};
+    for (int i = tid; i < N; i += RANSAC_FIN) {
+        const D3 a = load3(src, i), b = load3(tgt, i);
+        const bool in = ransac_d2(c, a.x, a.y, a.z, b.x, b.y, b.z) < r2;
+        if (labels) labels[i] = in ? 1.0f : 0.0f;
+        if (in) {
+            n += 1.0;
+            sa[0] += a.x, sa[1] += a.y, sa[2] += a.z;
+            sb[0] += b.x, sb[1] += b.y, sb[2] += b.z;
+        }
+    }
+    n = block_sum(n, red, tid);  // workgroup-uniform
+    if (n >= 3.0) {
+        refit_kabsch(src, tgt, N, r2, n, sa, sb, c, red, tid);
+        T[0] = c[0], T[1] = c[1], T[2] = c[2], T[3] = c[9];
+        T[4] = c[3], T[5] = c[4], T[6] = c[5], T[7] = c[10];
+        T[8] = c[6], T[9] = c[7], T[10] = c[8], T[11] = c[11];
+        T[12] = 0.0, T[13] = 0.0, T[14] = 0.0, T[15] = 1.0;
+    }
+    if (tid != 0) return;
+    for (int i = 0; i < 16; ++i) trans[i] = T[i];
+    if (trans_f32)
+        for (int i = 0; i < 16; ++i) trans_f32[i] = (float)T[i];
+    if (count) count[0] = (int)n;
+}
+
+hipError_t launch_refit_inliers(const double *pose, const float *src, const float *tgt, int N, double radius,
+                                double *trans, float *trans_f32, int *count, float *labels, hipStream_t s) {
+    hipLaunchKernelGGL(refit_inliers_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, pose, src, tgt, N, radius * radius, trans,
+                       trans_f32, count, labels);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------- launchers
