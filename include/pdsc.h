@@ -582,7 +582,7 @@ int32_t pdsc_ransac_correspondence(const float *src, const float *tgt, int32_t N
  * rev == NULL: only feat_dist is written (is_bb, norm, num_bb may be NULL).
  *
  * pdsc_gpf_select (matching.py:100-208 Grid_Prioritized_Filter, BB_first=False;
- * BB_first=True has no caller in the reference and is not built).  xyz0 [N0,3]
+ * BB_first=True, which algorithms/TEASER_plus_plus.py:110 calls, is not built).  xyz0 [N0,3]
  * are the source points of rows 0 .. N0-1, norm [N0] and num_bb as above.
  *   Cells     to_quads (:139-145) bit-exactly in fp32, in its operation order:
  *             q(X) = floor(G * ((X - m) / ((M - m) + 1e-3f))) with m, M the
@@ -642,6 +642,89 @@ int32_t pdsc_gpf_select(const float *xyz0, const float *norm, const int32_t *num
                         const pdsc_gpf_debug *debug, void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
 int32_t pdsc_refit_inliers(const double *pose, const float *src, const float *tgt, int32_t N, double radius,
                            double *trans, float *trans_f32, int32_t *count, float *labels, pdsc_stream_t stream);
+
+/* ------------------------------------------------- f8 PMC baseline ---------
+ * PMC of baseline_scripts/baseline_3DMatch.py:56-77: a graph over the N
+ * correspondences with an edge where two of them are length-consistent, its
+ * maximum clique as the inlier set, one Kabsch (a9) over it.  The reference
+ * builds the edge list in a Python double loop and hands it to a prebuilt x86
+ * libpmc.so (utils/max_clique.py:14-40); here both halves run on the device.
+ * The same two pieces are the core of TEASER++'s inlier selection
+ * (algorithms/TEASER_plus_plus.py:78-93, PMC_EXACT), which is not built.
+ * Nothing here synchronises the stream or allocates, every argument is checked
+ * on the host before any device work, and two calls are bitwise equal (integer
+ * work only; every output word has one writer).
+ *
+ * A graph `adj` is N rows of W = ceil(N / 64) uint64 words: bit j % 64 of word
+ * j / 64 of row i is set iff i != j and (i, j) is an edge; bits past N and the
+ * diagonal are 0; the matrix is symmetric.  1 <= N <= 8192
+ * (PDSC_ERR_UNSUPPORTED above: one wavefront holds a row).
+ *
+ * pdsc_consistency_graph: corr_pos [N,6] fp32, the loader's centred [src, tgt]
+ * rows.  With d = c_i[0:3] - c_j[0:3] and e = c_i[3:6] - c_j[3:6], all in fp32
+ * with every product and sum rounded (no contraction):
+ *   a = (dx*dx + dy*dy) + dz*dz,  b likewise of e   (np.sum of three squares);
+ *   PDSC_EDGE_SQUARED  diff = a - b: the reference as written (:66-67), which
+ *                      holds SQUARED lengths against inlier_threshold;
+ *   PDSC_EDGE_LENGTH   diff = sqrtf(a) - sqrtf(b) (correctly rounded), the
+ *                      | |s_i - s_j| - |t_i - t_j| | form of TEASER-style graphs;
+ *   edge iff (double)|diff| < threshold (numpy 1.x compares the fp32 scalar in
+ *   fp64).  The predicate is bit-symmetric in (i, j); the N x N values are
+ *   never stored.  degree [N] int32 (may be NULL) = the row's edges.
+ *   PDSC_ERR_ARG: N < 1, threshold <= 0 or not finite, an unknown mode, null
+ *   corr_pos / adj.
+ *
+ * pdsc_max_clique: a maximum clique of adj.  members [N capacity] = its
+ * vertices ascending, -1 past the size; labels [N] fp32 0/1 (may be NULL);
+ * *result (device memory, required).  The clique returned is a pure function
+ * of (adj, N, node_budget) -- which of several maximum cliques is this
+ * implementation's choice -- and never depends on timing.  A graph without
+ * edges gives {0}, size 1.
+ *   Lower bound  a greedy clique from every vertex (candidates = its
+ *                neighbours; take the candidate of the highest degree, ties to
+ *                the lower index; intersect; repeat); the best by (size, lower
+ *                start) is the first incumbent, heuristic_size its size.
+ *   Reduction    16 rounds of dropping every vertex with fewer neighbours left
+ *                than the incumbent's size; the survivors in ascending
+ *                (remaining degree, index) order are the roots.
+ *   Search       root r searches the cliques whose first member in that order
+ *                is r, by branch and bound on bitsets with a greedy-colouring
+ *                bound, from the incumbent of its launch; the roots run in
+ *                four launches, each from the previous one's winner by (size,
+ *                lower root).
+ *   Budget       every colouring is one expanded node.  A root stops after
+ *                node_budget nodes (0: pdsc_max_clique_default_budget()), or
+ *                where its stack would pass pdsc_max_clique_depth() levels
+ *                (a clique more than that many vertices beyond its root);
+ *                either way it counts in roots_incomplete, exact becomes 0, and
+ *                the best clique found so far is still returned.  exact == 1:
+ *                size is the clique number.  nodes = the sum over the roots.
+ *   PDSC_ERR_ARG: N < 1, node_budget < 0, null adj / members / result /
+ *   workspace, a workspace that is too small.
+ * pdsc_greedy_clique: the lower bound alone (same outputs and workspace;
+ * exact = 0, roots_incomplete = 0, nodes = 0).                                */
+enum pdsc_edge_mode {
+    PDSC_EDGE_SQUARED = 0,
+    PDSC_EDGE_LENGTH = 1,
+};
+typedef struct pdsc_clique_result { /* device memory, written by the call */
+    int32_t size;                   /* members of the clique returned */
+    int32_t exact;                  /* 1: every root was searched to the end, size is the clique number */
+    int32_t heuristic_size;         /* the greedy lower bound */
+    int32_t roots_incomplete;       /* roots stopped by the budget or the stack depth */
+    int64_t nodes;                  /* expanded search nodes over all roots */
+} pdsc_clique_result;
+int32_t pdsc_consistency_graph(const float *corr_pos, int32_t N, double threshold, int32_t mode, uint64_t *adj,
+                               int32_t *degree /* may be NULL */, pdsc_stream_t stream);
+int32_t pdsc_max_clique_depth(void);          /* stack levels per root */
+int64_t pdsc_max_clique_default_budget(void); /* nodes per root */
+size_t  pdsc_max_clique_workspace_bytes(int32_t N);
+int32_t pdsc_max_clique(const uint64_t *adj, int32_t N, int64_t node_budget, int32_t *members,
+                        pdsc_clique_result *result, float *labels /* may be NULL */, void *workspace,
+                        size_t workspace_bytes, pdsc_stream_t stream);
+int32_t pdsc_greedy_clique(const uint64_t *adj, int32_t N, int32_t *members, pdsc_clique_result *result,
+                           float *labels /* may be NULL */, void *workspace, size_t workspace_bytes,
+                           pdsc_stream_t stream);
 
 /* ----------------------------------------------- full testing forward ------
  * PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197)

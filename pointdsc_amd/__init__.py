@@ -6,7 +6,8 @@
 row); ``pointdsc_amd.ransac`` is RANSAC on correspondences (the drivers' RANSAC
 baseline and ``--solver RANSAC``); ``pointdsc_amd.matching`` / ``pointdsc_amd.fr``
 are the fork's correspondence filters (MFR, GPF) and its filtered RANSAC ``FR``;
-the C ABI is ``include/pdsc.h`` /
+``pointdsc_amd.baselines`` holds the baselines ``SM``, ``RANSAC`` and ``PMC``
+(consistency graph + maximum clique); the C ABI is ``include/pdsc.h`` /
 ``pointdsc_amd/libpdsc.so``.
 """
 __version__ = "0.1.0"
@@ -16,10 +17,14 @@ _RANSAC = ("registration_ransac_based_on_correspondence", "ransac_solver")
 _MATCHING = ("find_nn", "find_2nn", "nn_to_mutual", "mark_best_buddies", "calc_distance_ratio_in_feature_space",
              "Grid_Prioritized_Filter", "measure_inlier_ratio", "refit_inliers")
 _FR = ("FR",)
-__all__ = [*_ICP, *_RANSAC, *_MATCHING, *_FR]
+_PMC = ("PMC",)
+__all__ = [*_ICP, *_RANSAC, *_MATCHING, *_FR, *_PMC]
 
 
-def __getattr__(name):  # the ICP / RANSAC / FR entry points, without importing torch on `import pointdsc_amd`
+def __getattr__(name):  # the ICP / RANSAC / FR / PMC entry points, without importing torch on `import pointdsc_amd`
+    if name in _PMC:
+        from . import baselines
+        return getattr(baselines, name)
     if name in _MATCHING:
         from . import matching
         return getattr(matching, name)

@@ -65,6 +65,16 @@ class PdscGpfDebug(ctypes.Structure):
     _fields_ = [("cell", vp), ("max_per_quad", vp), ("per_quad", vp), ("height", vp)]
 
 
+class PdscCliqueResult(ctypes.Structure):
+    """``struct pdsc_clique_result`` (include/pdsc.h): 24 bytes of device memory."""
+    _fields_ = [("size", c_int32), ("exact", c_int32), ("heuristic_size", c_int32), ("roots_incomplete", c_int32),
+                ("nodes", ctypes.c_int64)]
+
+
+# enum pdsc_edge_mode (include/pdsc.h)
+EDGE_MODES = {"squared": 0, "length": 1}
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "pdsc_version": (ctypes.c_char_p, []),
@@ -141,6 +151,12 @@ _PROTOS = {
     "pdsc_gpf_select": (c_int32, [vp, vp, vp, c_int32, c_int32, c_double, vp, vp, vp, ctypes.POINTER(PdscGpfDebug),
                                   vp, c_size_t, vp]),
     "pdsc_refit_inliers": (c_int32, [vp, vp, vp, c_int32, c_double, vp, vp, vp, vp, vp]),
+    "pdsc_consistency_graph": (c_int32, [vp, c_int32, c_double, c_int32, vp, vp, vp]),
+    "pdsc_max_clique_depth": (c_int32, []),
+    "pdsc_max_clique_default_budget": (ctypes.c_int64, []),
+    "pdsc_max_clique_workspace_bytes": (c_size_t, [c_int32]),
+    "pdsc_max_clique": (c_int32, [vp, c_int32, ctypes.c_int64, vp, vp, vp, vp, c_size_t, vp]),
+    "pdsc_greedy_clique": (c_int32, [vp, c_int32, vp, vp, vp, vp, c_size_t, vp]),
     "pdsc_forward_training_workspace_bytes": (c_size_t, [CFG, c_int32, c_int32]),
     "pdsc_range_status": (c_int32, [vp, c_int32, ctypes.POINTER(c_int32), vp]),
     "pdsc_range_poll": (c_int32, [vp, c_int32, vp]),

@@ -1,4 +1,4 @@
-"""Spectral-matching baseline on the GPU.
+"""The reference's baselines on the GPU: SM, RANSAC, PMC.
 
 ``SM(corr, src_keypts, tgt_keypts, ...)`` mirrors
 baseline_scripts/baseline_3DMatch.py:19-53 -- same inputs (``corr`` is the
@@ -54,6 +54,32 @@ def RANSAC(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, max_ite
     res = registration_ransac_based_on_correspondence(src[0], tgt[0], None, inlier_threshold, ransac_n=4,
                                                       max_iteration=max_iteration, seed=seed)
     return res.transformation_f32[None], res.labels[None]
+
+
+def PMC(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, mode: str = "squared", node_budget: int = 0,
+        return_info: bool = False):
+    """baseline_scripts/baseline_3DMatch.py:56-77: the graph of length-consistent
+    correspondence pairs over ``corr`` (the loader's ``corr_pos`` [1,N,6]), its
+    maximum clique as the inlier set and one Kabsch over it.  Same outputs as
+    ``SM``: ``(pred_trans [1,4,4], pred_labels [1,N])``; ``return_info=True``
+    appends the search's ``CliqueInfo`` (size, exact, heuristic_size,
+    roots_incomplete, nodes; reading it synchronises).  mode 'squared' is the
+    reference as written (squared lengths against ``inlier_threshold``),
+    'length' compares the lengths.  Runs on pointdsc_amd/csrc/clique.hip
+    (pdsc_consistency_graph, pdsc_max_clique) where the reference calls a
+    prebuilt x86 libpmc.so; ``node_budget`` bounds each root's search (0: the
+    library default).  No CPU fallback."""
+    from .kernels import CliqueInfo, consistency_graph, max_clique, rigid_transform_3d
+    corr, src, tgt = _dev(corr, "corr"), _dev(src_keypts, "src_keypts"), _dev(tgt_keypts, "tgt_keypts")
+    assert corr.shape[0] == 1, "PMC: bs = 1 (baseline_3DMatch.py:73)"
+    N = corr.shape[1]
+    if corr.shape != (1, N, 6) or src.shape != (1, N, 3) or tgt.shape != (1, N, 3):
+        raise ValueError(f"shapes {tuple(corr.shape)} {tuple(src.shape)} {tuple(tgt.shape)}")
+    adj, _ = consistency_graph(corr[0], inlier_threshold, mode)
+    _, labels, result = max_clique(adj, node_budget)
+    pred_labels = labels[None]
+    pred_trans = rigid_transform_3d(src, tgt, pred_labels)
+    return (pred_trans, pred_labels, CliqueInfo(result)) if return_info else (pred_trans, pred_labels)
 
 
 def sm_matvec(M, v):

@@ -1315,6 +1315,49 @@ int32_t pdsc_refit_inliers(const double *pose, const float *src, const float *tg
     return PDSC_OK;
 }
 
+// ------------------------------------------------------------ f8 PMC baseline
+int32_t pdsc_consistency_graph(const float *corr_pos, int32_t N, double threshold, int32_t mode, uint64_t *adj,
+                               int32_t *degree, pdsc_stream_t stream) {
+    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
+    if (N > CLIQUE_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, CLIQUE_MAX_N);
+    if (!(threshold > 0.0) || !std::isfinite(threshold))
+        return fail(PDSC_ERR_ARG, "threshold %g must be > 0 and finite", threshold);
+    if (mode != PDSC_EDGE_SQUARED && mode != PDSC_EDGE_LENGTH)
+        return fail(PDSC_ERR_ARG, "mode=%d (PDSC_EDGE_SQUARED or PDSC_EDGE_LENGTH)", mode);
+    if (!corr_pos || !adj) return fail(PDSC_ERR_ARG, "null pointer");
+    HIPCHK(launch_consistency_graph(corr_pos, N, threshold, mode == PDSC_EDGE_LENGTH,
+                                    reinterpret_cast<unsigned long long *>(adj), degree, S_(stream)));
+    return PDSC_OK;
+}
+
+int32_t pdsc_max_clique_depth(void) { return clique_depth(); }
+int64_t pdsc_max_clique_default_budget(void) { return CLIQUE_DEFAULT_BUDGET; }
+
+size_t pdsc_max_clique_workspace_bytes(int32_t N) { return N < 1 || N > CLIQUE_MAX_N ? 0 : clique_workspace_bytes(N); }
+
+static int32_t clique_call(const uint64_t *adj, int32_t N, int64_t node_budget, bool exact, int32_t *members,
+                           pdsc_clique_result *result, float *labels, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
+    if (N > CLIQUE_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, CLIQUE_MAX_N);
+    if (node_budget < 0) return fail(PDSC_ERR_ARG, "node_budget=%lld (need >= 0; 0: the default)", (long long)node_budget);
+    if (!adj || !members || !result || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_max_clique_workspace_bytes(N)));
+    HIPCHK(launch_max_clique(reinterpret_cast<const unsigned long long *>(adj), N,
+                             node_budget ? (long long)node_budget : CLIQUE_DEFAULT_BUDGET, exact, members, result, labels,
+                             ws, S_(stream)));
+    return PDSC_OK;
+}
+
+int32_t pdsc_max_clique(const uint64_t *adj, int32_t N, int64_t node_budget, int32_t *members,
+                        pdsc_clique_result *result, float *labels, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    return clique_call(adj, N, node_budget, true, members, result, labels, ws, ws_bytes, stream);
+}
+
+int32_t pdsc_greedy_clique(const uint64_t *adj, int32_t N, int32_t *members, pdsc_clique_result *result, float *labels,
+                           void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    return clique_call(adj, N, 0, false, members, result, labels, ws, ws_bytes, stream);
+}
+
 // ------------------------------------------------- f1 correspondence construction
 size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
     return align_bytes((size_t)Ns * 8) + align_bytes((size_t)Nt * 8);

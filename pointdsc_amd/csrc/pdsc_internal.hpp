@@ -360,6 +360,17 @@ hipError_t launch_gpf_select(const float *xyz0, const float *norm, const int *nu
                              int *kept, int *count, float *kept_norm, const pdsc_gpf_debug *debug, void *ws,
                              hipStream_t s);
 
+// PMC baseline (clique.hip, f8): adj is N rows of ceil(N / 64) 64-bit words
+constexpr int CLIQUE_MAX_N = 8192;                    // one wavefront holds a row in two words per lane
+constexpr long long CLIQUE_DEFAULT_BUDGET = 1 << 12;  // expanded nodes per root (DESIGN.md §7 "PMC baseline")
+hipError_t launch_consistency_graph(const float *corr_pos, int N, double thr, bool length, unsigned long long *adj,
+                                    int *degree, hipStream_t s);
+int clique_depth();
+size_t clique_workspace_bytes(int N);
+// exact = false: the greedy lower bound alone
+hipError_t launch_max_clique(const unsigned long long *adj, int N, long long budget, bool exact, int *members,
+                             pdsc_clique_result *res, float *labels, void *ws, hipStream_t s);
+
 // correspondence construction (corr.hip)
 #define HIP_RET(expr)                        \
     do {                                      \

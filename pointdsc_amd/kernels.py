@@ -409,6 +409,66 @@ def spectral_matching_loss(M, gt_labels, balanced=True):
     return loss
 
 
+# --------------------------------------------------------------------- f8
+def consistency_graph(corr_pos, threshold: float, mode: str = "squared"):
+    """The PMC baseline's graph (include/pdsc.h f8, baseline_3DMatch.py:60-68):
+    ``(adj int64 [N, ceil(N/64)], degree int32 [N])`` for corr_pos [N,6]; bit
+    j % 64 of word j // 64 of row i is set iff i != j and the pair is
+    consistent.  mode 'squared' is the reference as written, 'length' the
+    difference of the lengths themselves."""
+    corr_pos = _dev(corr_pos, "corr_pos")
+    if corr_pos.dim() != 2 or corr_pos.shape[1] != 6:
+        raise ValueError(f"corr_pos {tuple(corr_pos.shape)} must be [N,6]")
+    if mode not in _lib.EDGE_MODES:
+        raise ValueError(f"mode must be one of {sorted(_lib.EDGE_MODES)}, got {mode!r}")
+    N, dev = corr_pos.shape[0], corr_pos.device
+    adj = torch.empty((N, (N + 63) // 64), dtype=torch.int64, device=dev)
+    degree = torch.empty(N, dtype=torch.int32, device=dev)
+    check(_lib.load().pdsc_consistency_graph(_p(corr_pos), N, float(threshold), _lib.EDGE_MODES[mode], _p(adj),
+                                             _p(degree), _stream(dev)), "pdsc_consistency_graph")
+    return adj, degree
+
+
+class CliqueInfo:
+    """``pdsc_clique_result`` read back from the device (one synchronising copy)."""
+    __slots__ = ("size", "exact", "heuristic_size", "roots_incomplete", "nodes")
+
+    def __init__(self, result: torch.Tensor):
+        r = _lib.PdscCliqueResult.from_buffer_copy(result.cpu().numpy().tobytes())
+        self.size, self.exact, self.heuristic_size = int(r.size), int(r.exact), int(r.heuristic_size)
+        self.roots_incomplete, self.nodes = int(r.roots_incomplete), int(r.nodes)
+
+    def __repr__(self):
+        return "CliqueInfo(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+
+
+def max_clique(adj, node_budget: int = 0, heuristic_only: bool = False):
+    """A maximum clique of the bitset graph adj int64 [N, ceil(N/64)] (include/pdsc.h
+    f8): ``(members int32 [N], labels fp32 [N], result)`` -- members ascending
+    and -1 past the size, result the device copy of ``pdsc_clique_result`` (an
+    int32 [6] tensor; ``CliqueInfo(result)`` reads it).  node_budget: expanded
+    nodes per root, 0 = the library default.  heuristic_only: the greedy lower
+    bound alone (pdsc_greedy_clique)."""
+    adj = _dev(adj, "adj", torch.int64)
+    N = adj.shape[0]
+    if adj.dim() != 2 or adj.shape[1] != (N + 63) // 64:
+        raise ValueError(f"adj {tuple(adj.shape)} must be [N, ceil(N/64)]")
+    dev = adj.device
+    L = _lib.load()
+    nb = L.pdsc_max_clique_workspace_bytes(N)
+    ws = _workspace(nb, dev)
+    members = torch.empty(N, dtype=torch.int32, device=dev)
+    labels = torch.empty(N, dtype=torch.float32, device=dev)
+    result = torch.empty(6, dtype=torch.int32, device=dev)
+    if heuristic_only:
+        check(L.pdsc_greedy_clique(_p(adj), N, _p(members), _p(result), _p(labels), _p(ws), nb, _stream(dev)),
+              "pdsc_greedy_clique")
+    else:
+        check(L.pdsc_max_clique(_p(adj), N, int(node_budget), _p(members), _p(result), _p(labels), _p(ws), nb,
+                                _stream(dev)), "pdsc_max_clique")
+    return members, labels, result
+
+
 class ForwardPlan:
     """Reusable workspace + outputs for repeated batched forwards of one (B, N).
 
