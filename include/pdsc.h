@@ -582,7 +582,7 @@ int32_t pdsc_ransac_correspondence(const float *src, const float *tgt, int32_t N
  * rev == NULL: only feat_dist is written (is_bb, norm, num_bb may be NULL).
  *
  * pdsc_gpf_select (matching.py:100-208 Grid_Prioritized_Filter, BB_first=False;
- * BB_first=True, which algorithms/TEASER_plus_plus.py:110 calls, is not built).  xyz0 [N0,3]
+ * BB_first=True, which algorithms/TEASER_plus_plus.py:110 calls, is composed from it in f9).  xyz0 [N0,3]
  * are the source points of rows 0 .. N0-1, norm [N0] and num_bb as above.
  *   Cells     to_quads (:139-145) bit-exactly in fp32, in its operation order:
  *             q(X) = floor(G * ((X - m) / ((M - m) + 1e-3f))) with m, M the
@@ -650,7 +650,7 @@ int32_t pdsc_refit_inliers(const double *pose, const float *src, const float *tg
  * builds the edge list in a Python double loop and hands it to a prebuilt x86
  * libpmc.so (utils/max_clique.py:14-40); here both halves run on the device.
  * The same two pieces are the core of TEASER++'s inlier selection
- * (algorithms/TEASER_plus_plus.py:78-93, PMC_EXACT), which is not built.
+ * (algorithms/TEASER_plus_plus.py:78-93, PMC_EXACT): f9 below builds on them.
  * Nothing here synchronises the stream or allocates, every argument is checked
  * on the host before any device work, and two calls are bitwise equal (integer
  * work only; every output word has one writer).
@@ -725,6 +725,113 @@ int32_t pdsc_max_clique(const uint64_t *adj, int32_t N, int64_t node_budget, int
 int32_t pdsc_greedy_clique(const uint64_t *adj, int32_t N, int32_t *members, pdsc_clique_result *result,
                            float *labels /* may be NULL */, void *workspace, size_t workspace_bytes,
                            pdsc_stream_t stream);
+
+/* ------------------------------------------------------ f9 TEASER++ --------
+ * The fork's --algo TEASER (algorithms/TEASER_plus_plus.py:78-93: cbar2 = 1,
+ * noise_bound = 0.3, no scale estimation, PMC_EXACT, CHAIN, GNC_TLS with
+ * gnc_factor 1.4, max_iterations 10000, cost_threshold 1e-16) after f8's graph
+ * and clique: the GNC-TLS rotation over the clique's TIM chain and the
+ * component-wise TLS translation by adaptive voting.  The reference calls the
+ * x86 library teaserpp_python, which is neither installed nor in the reference
+ * tree: the definitions below are written from the published algorithm and ARE
+ * the contract; parity with the TEASER++ library itself is unpinned.
+ * Nothing here synchronises the stream or allocates; every argument is checked
+ * on the host before any device work (PDSC_ERR_ARG: K or N < 1, null pointers,
+ * noise_bound not finite or <= 0, gnc_factor <= 1 or not finite, max_iterations
+ * < 1, a cost_threshold that is NaN, node_budget < 0, a workspace that is too
+ * small; PDSC_ERR_UNSUPPORTED: K or N > 8192).  All arithmetic is fp64 with no
+ * contraction, every sum runs through one fixed tree and there are no
+ * floating-point atomics: two calls are bitwise equal.
+ *
+ * pdsc_gnc_tls_rotation: src_tims, dst_tims [K,3] fp64 (a_j, b_j), 1 <= K <=
+ * 8192.  nb2 = noise_bound^2, w = 1, prev = +inf; for i = 0 .. max_iterations-1:
+ *   1. H = sum_j w_j a_j b_j^T (no centring: TIMs are differences), H = U S V^T,
+ *      R = V diag(1, 1, det(V U^T)) U^T by a9's fp64 Jacobi solve.  Where H has
+ *      rank < 2 the rotation is not determined by the data (K = 1; two opposite
+ *      TIMs): R is then that solve's deterministic completion.
+ *   2. r_j = |b_j - R a_j|^2.
+ *   3. at i == 0: d = 2 max_j r_j / nb2 - 1; d <= 0 stops here with every weight
+ *      1 (stop_reason 1, iterations 1); else mu = 1 / d.  Deviation: the library
+ *      tests mu <= 0 after the division, which differs only at d == 0, where it
+ *      goes on with mu = inf and NaN thresholds.
+ *   4. th1 = (mu + 1) / mu * nb2, th2 = mu / (mu + 1) * nb2; cost = sum_j w_j r_j
+ *      with the OLD weights; then w_j = 0 where r_j >= th1, 1 where r_j <= th2,
+ *      else sqrt(nb2 mu (mu + 1) / r_j) - mu.
+ *   5. diff = |cost - prev|, mu *= gnc_factor, prev = cost; diff < cost_threshold
+ *      stops (stop_reason 2).
+ * R [9] row-major; weights [K] (may be NULL); inliers [K] int32 = (w_j >= 0.5)
+ * (may be NULL); info (device, may be NULL): iterations = passes of step 1,
+ * cost = the last step 4 sum (step 3's stop: sum r_j), mu after the last step 5
+ * (0 after step 3's stop), stop_reason 0 = max_iterations reached.  One launch
+ * of one workgroup; no host read between iterations.
+ *
+ * pdsc_tls_translation: src [K,3] fp64 (already rotated), dst [K,3] fp64.  Per
+ * axis c: x_j = dst_jc - src_jc, beta = noise_bound for every j (cbar2 = 1).
+ * The 2K events (x_j - beta, tag +(j+1)) "enter" and (x_j + beta, tag -(j+1))
+ * "leave", ascending by value, ties by tag; after each event C = the entered-
+ * and-not-left indices; an event that leaves C empty is skipped; else xhat =
+ * mean(x_C), cost = sum_{j in C} (x_j - xhat)^2 + beta (K - |C|) (the library's
+ * mixed-unit cost, kept as is); t_c = xhat of the first event of minimal cost.
+ * With one beta, C is a window of the sorted x: the kernel sorts x, derives
+ * every event's window and place in the sequence, and takes window sums from
+ * prefix sums of (x - x_median) and its square.  Deviation: two events of
+ * DIFFERENT x whose x -/+ beta round to the same fp64 value are ordered by x,
+ * then leave before enter, where the tag order could interleave them (events of
+ * equal x give the same sets of values either way).  inliers [K] int32 (may be
+ * NULL) = |x_jc - t_c| <= beta on all three axes.  Workspace:
+ * pdsc_tls_translation_workspace_bytes(K) (the prefix sums).
+ *
+ * pdsc_teaser_solve: src, tgt [N,3] fp32, row i <-> row i, 1 <= N <= 8192; all
+ * enqueued in one go, no host read in between:
+ *   1. pdsc_consistency_graph on the rows [src_i, tgt_i], PDSC_EDGE_LENGTH,
+ *      threshold 2 noise_bound.  Deviation: TEASER++ tests <= on fp64 lengths;
+ *      this is f8's strict < on correctly rounded fp32 lengths.
+ *   2. pdsc_max_clique with node_budget (0: the default).  The reference's
+ *      FAIL_TOLERANT watchdog kills a stuck search after 10 s; here the budget
+ *      is that bound: an incomplete search still gives a pose, clique_exact = 0.
+ *   3. Kc = the clique's size, read on the device.  Kc <= 1 is the library's
+ *      "clique too small": valid = 0, trans = I, labels 0, and the solver
+ *      kernels return at entry.  Else the CHAIN TIMs over the members c_0 < ...
+ *      < c_{Kc-1}: a_i = src[c_{(i+1) mod Kc}] - src[c_i], b_i likewise from tgt
+ *      (Kc TIMs; Kc = 2 gives two opposite ones, as in the library).
+ *   4. the rotation above on them;  5. s_i = R src[c_i];  6. the translation
+ *      above on (s_i, tgt[c_i]).
+ * result (device memory, required); trans_f32 [4,4] (may be NULL) = (float)
+ * trans; labels [N] fp32 (may be NULL) = 1 for clique members that are
+ * translation inliers.  Out of scope: scale estimation, the FGR rotation solver,
+ * the COMPLETE and STAR TIM graphs, the heuristic / KCORE clique modes,
+ * certification.                                                             */
+typedef struct pdsc_gnc_info { /* device memory, written by the call */
+    int32_t iterations;        /* passes of step 1 */
+    int32_t stop_reason;       /* 0 max_iterations, 1 no residual above the bound at pass 0, 2 cost converged */
+    double  cost;
+    double  mu;
+} pdsc_gnc_info;
+typedef struct pdsc_teaser_result { /* device memory, written by the call */
+    double  trans[16];              /* row-major 4x4 */
+    int32_t valid;                  /* 0: clique of fewer than 2 members, trans = I */
+    int32_t clique_size;
+    int32_t clique_exact;
+    int32_t roots_incomplete;
+    int32_t gnc_iterations;
+    int32_t n_rotation_inliers;     /* TIMs of the chain with final weight >= 0.5 */
+    int32_t n_translation_inliers;
+    int32_t reserved;
+} pdsc_teaser_result;
+int32_t pdsc_gnc_tls_rotation(const double *src_tims, const double *dst_tims, int32_t K, double noise_bound,
+                              double gnc_factor, int32_t max_iterations, double cost_threshold, double *R,
+                              double *weights /* may be NULL */, int32_t *inliers /* may be NULL */,
+                              pdsc_gnc_info *info /* may be NULL */, pdsc_stream_t stream);
+size_t  pdsc_tls_translation_workspace_bytes(int32_t K);
+int32_t pdsc_tls_translation(const double *src, const double *dst, int32_t K, double noise_bound, double *t,
+                             int32_t *inliers /* may be NULL */, void *workspace, size_t workspace_bytes,
+                             pdsc_stream_t stream);
+size_t  pdsc_teaser_solve_workspace_bytes(int32_t N);
+int32_t pdsc_teaser_solve(const float *src, const float *tgt, int32_t N, double noise_bound, double gnc_factor,
+                          int32_t max_iterations, double cost_threshold, int64_t node_budget,
+                          pdsc_teaser_result *result, float *trans_f32 /* may be NULL */,
+                          float *labels /* may be NULL */, void *workspace, size_t workspace_bytes,
+                          pdsc_stream_t stream);
 
 /* ----------------------------------------------- full testing forward ------
  * PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197)

@@ -7,7 +7,8 @@ row); ``pointdsc_amd.ransac`` is RANSAC on correspondences (the drivers' RANSAC
 baseline and ``--solver RANSAC``); ``pointdsc_amd.matching`` / ``pointdsc_amd.fr``
 are the fork's correspondence filters (MFR, GPF) and its filtered RANSAC ``FR``;
 ``pointdsc_amd.baselines`` holds the baselines ``SM``, ``RANSAC`` and ``PMC``
-(consistency graph + maximum clique); the C ABI is ``include/pdsc.h`` /
+(consistency graph + maximum clique); ``pointdsc_amd.teaser`` is the fork's
+``TEASER`` (graph, clique, GNC-TLS rotation, TLS translation); the C ABI is ``include/pdsc.h`` /
 ``pointdsc_amd/libpdsc.so``.
 """
 __version__ = "0.1.0"
@@ -18,10 +19,14 @@ _MATCHING = ("find_nn", "find_2nn", "nn_to_mutual", "mark_best_buddies", "calc_d
              "Grid_Prioritized_Filter", "measure_inlier_ratio", "refit_inliers")
 _FR = ("FR",)
 _PMC = ("PMC",)
-__all__ = [*_ICP, *_RANSAC, *_MATCHING, *_FR, *_PMC]
+_TEASER = ("TEASER",)
+__all__ = [*_ICP, *_RANSAC, *_MATCHING, *_FR, *_PMC, *_TEASER]
 
 
-def __getattr__(name):  # the ICP / RANSAC / FR / PMC entry points, without importing torch on `import pointdsc_amd`
+def __getattr__(name):  # the ICP / RANSAC / FR / PMC / TEASER entry points, without importing torch on `import pointdsc_amd`
+    if name in _TEASER:
+        from . import teaser
+        return getattr(teaser, name)
     if name in _PMC:
         from . import baselines
         return getattr(baselines, name)

@@ -71,6 +71,18 @@ class PdscCliqueResult(ctypes.Structure):
                 ("nodes", ctypes.c_int64)]
 
 
+class PdscGncInfo(ctypes.Structure):
+    """``struct pdsc_gnc_info`` (include/pdsc.h): 24 bytes of device memory."""
+    _fields_ = [("iterations", c_int32), ("stop_reason", c_int32), ("cost", c_double), ("mu", c_double)]
+
+
+class PdscTeaserResult(ctypes.Structure):
+    """``struct pdsc_teaser_result`` (include/pdsc.h): 160 bytes of device memory."""
+    _fields_ = [("trans", c_double * 16), ("valid", c_int32), ("clique_size", c_int32), ("clique_exact", c_int32),
+                ("roots_incomplete", c_int32), ("gnc_iterations", c_int32), ("n_rotation_inliers", c_int32),
+                ("n_translation_inliers", c_int32), ("reserved", c_int32)]
+
+
 # enum pdsc_edge_mode (include/pdsc.h)
 EDGE_MODES = {"squared": 0, "length": 1}
 
@@ -157,6 +169,12 @@ _PROTOS = {
     "pdsc_max_clique_workspace_bytes": (c_size_t, [c_int32]),
     "pdsc_max_clique": (c_int32, [vp, c_int32, ctypes.c_int64, vp, vp, vp, vp, c_size_t, vp]),
     "pdsc_greedy_clique": (c_int32, [vp, c_int32, vp, vp, vp, vp, c_size_t, vp]),
+    "pdsc_gnc_tls_rotation": (c_int32, [vp, vp, c_int32, c_double, c_double, c_int32, c_double, vp, vp, vp, vp, vp]),
+    "pdsc_tls_translation_workspace_bytes": (c_size_t, [c_int32]),
+    "pdsc_tls_translation": (c_int32, [vp, vp, c_int32, c_double, vp, vp, vp, c_size_t, vp]),
+    "pdsc_teaser_solve_workspace_bytes": (c_size_t, [c_int32]),
+    "pdsc_teaser_solve": (c_int32, [vp, vp, c_int32, c_double, c_double, c_int32, c_double, ctypes.c_int64, vp, vp,
+                                    vp, vp, c_size_t, vp]),
     "pdsc_forward_training_workspace_bytes": (c_size_t, [CFG, c_int32, c_int32]),
     "pdsc_range_status": (c_int32, [vp, c_int32, ctypes.POINTER(c_int32), vp]),
     "pdsc_range_poll": (c_int32, [vp, c_int32, vp]),

@@ -1358,6 +1358,69 @@ int32_t pdsc_greedy_clique(const uint64_t *adj, int32_t N, int32_t *members, pds
     return clique_call(adj, N, 0, false, members, result, labels, ws, ws_bytes, stream);
 }
 
+// ---------------------------------------------------------------- f9 TEASER++
+static int32_t check_teaser_count(const char *what, int32_t n) {
+    if (n < 1) return fail(PDSC_ERR_ARG, "%s=%d (need >= 1)", what, n);
+    if (n > TEASER_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "%s=%d > %d", what, n, TEASER_MAX_N);
+    return PDSC_OK;
+}
+
+static int32_t check_noise_bound(double noise_bound) {
+    if (!(noise_bound > 0.0) || !std::isfinite(noise_bound))
+        return fail(PDSC_ERR_ARG, "noise_bound %g must be > 0 and finite", noise_bound);
+    return PDSC_OK;
+}
+
+static int32_t check_gnc(double gnc_factor, int32_t max_iterations, double cost_threshold) {
+    if (!(gnc_factor > 1.0) || !std::isfinite(gnc_factor))
+        return fail(PDSC_ERR_ARG, "gnc_factor %g must be > 1 and finite", gnc_factor);
+    if (max_iterations < 1) return fail(PDSC_ERR_ARG, "max_iterations=%d (need >= 1)", max_iterations);
+    if (cost_threshold != cost_threshold) return fail(PDSC_ERR_ARG, "cost_threshold is NaN");
+    return PDSC_OK;
+}
+
+int32_t pdsc_gnc_tls_rotation(const double *src_tims, const double *dst_tims, int32_t K, double noise_bound,
+                              double gnc_factor, int32_t max_iterations, double cost_threshold, double *R,
+                              double *weights, int32_t *inliers, pdsc_gnc_info *info, pdsc_stream_t stream) {
+    RET_IF(check_teaser_count("K", K));
+    RET_IF(check_noise_bound(noise_bound));
+    RET_IF(check_gnc(gnc_factor, max_iterations, cost_threshold));
+    if (!src_tims || !dst_tims || !R) return fail(PDSC_ERR_ARG, "null pointer");
+    HIPCHK(launch_gnc_rotation(src_tims, dst_tims, K, nullptr, noise_bound, gnc_factor, max_iterations, cost_threshold,
+                               R, weights, inliers, info, S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_tls_translation_workspace_bytes(int32_t K) { return K < 1 || K > TEASER_MAX_N ? 0 : tls_workspace_bytes(K); }
+
+int32_t pdsc_tls_translation(const double *src, const double *dst, int32_t K, double noise_bound, double *t,
+                             int32_t *inliers, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_teaser_count("K", K));
+    RET_IF(check_noise_bound(noise_bound));
+    if (!src || !dst || !t || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_tls_translation_workspace_bytes(K)));
+    HIPCHK(launch_tls_translation(src, dst, K, nullptr, noise_bound, t, inliers, ws, S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_teaser_solve_workspace_bytes(int32_t N) { return N < 1 || N > TEASER_MAX_N ? 0 : teaser_workspace_bytes(N); }
+
+int32_t pdsc_teaser_solve(const float *src, const float *tgt, int32_t N, double noise_bound, double gnc_factor,
+                          int32_t max_iterations, double cost_threshold, int64_t node_budget,
+                          pdsc_teaser_result *result, float *trans_f32, float *labels, void *ws, size_t ws_bytes,
+                          pdsc_stream_t stream) {
+    RET_IF(check_teaser_count("N", N));
+    RET_IF(check_noise_bound(noise_bound));
+    RET_IF(check_gnc(gnc_factor, max_iterations, cost_threshold));
+    if (node_budget < 0) return fail(PDSC_ERR_ARG, "node_budget=%lld (need >= 0; 0: the default)", (long long)node_budget);
+    if (!src || !tgt || !result || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_teaser_solve_workspace_bytes(N)));
+    HIPCHK(launch_teaser_solve(src, tgt, N, noise_bound, gnc_factor, max_iterations, cost_threshold,
+                               node_budget ? (long long)node_budget : CLIQUE_DEFAULT_BUDGET, result, trans_f32, labels,
+                               ws, S_(stream)));
+    return PDSC_OK;
+}
+
 // ------------------------------------------------- f1 correspondence construction
 size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
     return align_bytes((size_t)Ns * 8) + align_bytes((size_t)Nt * 8);

@@ -371,8 +371,22 @@ size_t clique_workspace_bytes(int N);
 hipError_t launch_max_clique(const unsigned long long *adj, int N, long long budget, bool exact, int *members,
                              pdsc_clique_result *res, float *labels, void *ws, hipStream_t s);
 
+// TEASER++ solvers (teaser.hip, f9).  Kdev != nullptr: the count is read on the device (0: return at entry) and
+// K is the capacity the launch is shaped for.
+constexpr int TEASER_MAX_N = CLIQUE_MAX_N;  // TIMs per thread of the one-workgroup rotation loop, LDS of the sort
+hipError_t launch_gnc_rotation(const double *A, const double *B, int K, const int *Kdev, double noise_bound,
+                               double factor, int max_iter, double cost_thr, double *R, double *weights, int *inliers,
+                               pdsc_gnc_info *info, hipStream_t s);
+size_t tls_workspace_bytes(int K);
+hipError_t launch_tls_translation(const double *src, const double *dst, int K, const int *Kdev, double noise_bound,
+                                  double *t, int *inliers, void *ws, hipStream_t s);
+size_t teaser_workspace_bytes(int N);
+hipError_t launch_teaser_solve(const float *src, const float *tgt, int N, double noise_bound, double factor,
+                               int max_iter, double cost_thr, long long budget, pdsc_teaser_result *res,
+                               float *trans_f32, float *labels, void *ws, hipStream_t s);
+
 // correspondence construction (corr.hip)
-#define HIP_RET(expr)                        \
+#define HIP_RET(expr)                      \
     do {                                      \
         hipError_t e_ = (expr);               \
         if (e_ != hipSuccess) return e_;      \

@@ -469,6 +469,98 @@ def max_clique(adj, node_budget: int = 0, heuristic_only: bool = False):
     return members, labels, result
 
 
+# --------------------------------------------------------------------- f9
+GNC_FACTOR, GNC_MAX_ITERATIONS, GNC_COST_THRESHOLD = 1.4, 10000, 1e-16  # TEASER_plus_plus.py:89-91
+
+
+class GncInfo:
+    """``pdsc_gnc_info`` read back from the device (one synchronising copy)."""
+    __slots__ = ("iterations", "stop_reason", "cost", "mu")
+
+    def __init__(self, info: torch.Tensor):
+        r = _lib.PdscGncInfo.from_buffer_copy(info.cpu().numpy().tobytes())
+        self.iterations, self.stop_reason, self.cost, self.mu = int(r.iterations), int(r.stop_reason), r.cost, r.mu
+
+    def __repr__(self):
+        return "GncInfo(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+
+
+class TeaserInfo:
+    """``pdsc_teaser_result`` read back from the device (one synchronising copy)."""
+    __slots__ = ("valid", "clique_size", "clique_exact", "roots_incomplete", "gnc_iterations", "n_rotation_inliers",
+                 "n_translation_inliers")
+
+    def __init__(self, result: torch.Tensor):
+        r = _lib.PdscTeaserResult.from_buffer_copy(result.cpu().numpy().tobytes())
+        for k in self.__slots__:
+            setattr(self, k, int(getattr(r, k)))
+
+    def __repr__(self):
+        return "TeaserInfo(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+
+
+def _tims(a, b, na, nb):
+    a, b = _dev(a, na, torch.float64), _dev(b, nb, torch.float64)
+    if a.dim() != 2 or a.shape[1] != 3 or a.shape != b.shape:
+        raise ValueError(f"{na} {tuple(a.shape)} / {nb} {tuple(b.shape)} must both be [K,3]")
+    return a, b
+
+
+def gnc_tls_rotation(src_tims, dst_tims, noise_bound: float, gnc_factor: float = GNC_FACTOR,
+                     max_iterations: int = GNC_MAX_ITERATIONS, cost_threshold: float = GNC_COST_THRESHOLD):
+    """pdsc_gnc_tls_rotation (include/pdsc.h f9) on fp64 TIMs [K,3]: ``(R fp64
+    [3,3], weights fp64 [K], inliers int32 [K], info)`` -- info the device copy of
+    ``pdsc_gnc_info`` (a uint8 [24] tensor; ``GncInfo(info)`` reads it and
+    synchronises)."""
+    a, b = _tims(src_tims, dst_tims, "src_tims", "dst_tims")
+    K, dev = a.shape[0], a.device
+    R = torch.empty((3, 3), dtype=torch.float64, device=dev)
+    w = torch.empty(K, dtype=torch.float64, device=dev)
+    inl = torch.empty(K, dtype=torch.int32, device=dev)
+    info = torch.empty(ctypes.sizeof(_lib.PdscGncInfo), dtype=torch.uint8, device=dev)
+    check(_lib.load().pdsc_gnc_tls_rotation(_p(a), _p(b), K, float(noise_bound), float(gnc_factor), int(max_iterations),
+                                            float(cost_threshold), _p(R), _p(w), _p(inl), _p(info), _stream(dev)),
+          "pdsc_gnc_tls_rotation")
+    return R, w, inl, info
+
+
+def tls_translation(src, dst, noise_bound: float):
+    """pdsc_tls_translation on fp64 points [K,3] (src already rotated):
+    ``(t fp64 [3], inliers int32 [K])``."""
+    a, b = _tims(src, dst, "src", "dst")
+    K, dev = a.shape[0], a.device
+    L = _lib.load()
+    nb = L.pdsc_tls_translation_workspace_bytes(K)
+    ws = _workspace(nb, dev)
+    t = torch.empty(3, dtype=torch.float64, device=dev)
+    inl = torch.empty(K, dtype=torch.int32, device=dev)
+    check(L.pdsc_tls_translation(_p(a), _p(b), K, float(noise_bound), _p(t), _p(inl), _p(ws), nb, _stream(dev)),
+          "pdsc_tls_translation")
+    return t, inl
+
+
+def teaser_solve(src, tgt, noise_bound: float, node_budget: int = 0, gnc_factor: float = GNC_FACTOR,
+                 max_iterations: int = GNC_MAX_ITERATIONS, cost_threshold: float = GNC_COST_THRESHOLD):
+    """pdsc_teaser_solve on matched fp32 points src[i] <-> tgt[i] [N,3]: ``(trans
+    fp64 [4,4], trans fp32 [4,4], labels fp32 [N], result)`` -- result the device
+    copy of ``pdsc_teaser_result`` (a uint8 [160] tensor whose first 128 bytes
+    are trans; ``TeaserInfo(result)`` reads the counters and synchronises)."""
+    src, tgt = _dev(src, "src"), _dev(tgt, "tgt")
+    if src.dim() != 2 or src.shape[1] != 3 or src.shape != tgt.shape:
+        raise ValueError(f"src {tuple(src.shape)} / tgt {tuple(tgt.shape)} must both be [N,3]")
+    N, dev = src.shape[0], src.device
+    L = _lib.load()
+    nb = L.pdsc_teaser_solve_workspace_bytes(N)
+    ws = _workspace(nb, dev)
+    result = torch.empty(ctypes.sizeof(_lib.PdscTeaserResult), dtype=torch.uint8, device=dev)
+    t32 = torch.empty((4, 4), dtype=torch.float32, device=dev)
+    labels = torch.empty(N, dtype=torch.float32, device=dev)
+    check(L.pdsc_teaser_solve(_p(src), _p(tgt), N, float(noise_bound), float(gnc_factor), int(max_iterations),
+                              float(cost_threshold), int(node_budget), _p(result), _p(t32), _p(labels), _p(ws), nb,
+                              _stream(dev)), "pdsc_teaser_solve")
+    return result[:128].view(torch.float64).view(4, 4), t32, labels, result
+
+
 class ForwardPlan:
     """Reusable workspace + outputs for repeated batched forwards of one (B, N).
 

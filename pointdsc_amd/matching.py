@@ -201,17 +201,34 @@ def calc_distance_ratio_in_feature_space(fcgf_feats0, fcgf_feats1, corres_idx0, 
 
 def Grid_Prioritized_Filter(fcgf_feats0, fcgf_feats1, corres_idx0, corres_idx1, idx1_2nd, xyz0, args, BB_first=False,
                             _rev=None):
-    """matching.py:100-208 with BB_first=False (the only form FR calls; the other
-    is not built): (corres_idx0, corres_idx1, idx1_2nd of the kept pairs, the
-    three inputs, norm_feat_dist of the kept pairs).  corres_idx0 must be the
-    full range 0 .. N0-1, as the reference assumes."""
-    if BB_first:
-        raise NotImplementedError("Grid_Prioritized_Filter(BB_first=True) has no caller in the reference; not built")
+    """matching.py:100-208: (corres_idx0, corres_idx1, idx1_2nd of the kept pairs,
+    the three inputs, norm_feat_dist of the kept pairs).  corres_idx0 must be the
+    full range 0 .. N0-1, as the reference assumes.
+
+    BB_first=False (FR's form): every pair is a candidate, best buddies first,
+    the total is GPF_factor * num_bb.  BB_first=True (TEASER's form, :112-116):
+    only the mutual pairs are candidates; all of them are returned (with None for
+    norm_feat_dist) when args.GPF_max_matches >= their number -- one host read, as
+    in the reference -- else the grid keeps GPF_max_matches of them, ranked by the
+    distance ratio normalised over the mutual pairs, without the best-buddy offset."""
     n0 = fcgf_feats0.shape[0]
     if corres_idx0.shape[0] != n0 or not torch.equal(corres_idx0, torch.arange(n0, device=corres_idx0.device,
                                                                                dtype=corres_idx0.dtype)):
         raise ValueError("corres_idx0 must be the full range 0 .. N0-1 of feats0's rows")
     rev = _rev if _rev is not None else nn2(fcgf_feats0, fcgf_feats1)[2]
+    if BB_first:
+        total = int(args.GPF_max_matches)
+        i0, i1, i2 = nn_to_mutual(fcgf_feats0, fcgf_feats1, corres_idx0, corres_idx1, idx1_2nd, force_return_2nd=True,
+                                  _rev=rev)
+        if total >= i0.shape[0]:
+            return i0, i1, i2, corres_idx0, corres_idx1, idx1_2nd, None
+        fd = match_ratio(_dev(fcgf_feats0, "feats0")[i0], fcgf_feats1, i1, i2)[0]
+        m, M = fd.min(), fd.max()
+        norm = torch.where(M > m, (fd - m) / (M - m), torch.zeros_like(fd))  # max == min: 0, as pdsc_match_ratio
+        num = torch.full((1,), total, dtype=torch.int32, device=fd.device)
+        kept, kept_norm, _ = gpf_select(_dev(xyz0, "xyz0")[i0], norm, num, args.GPF_grid_wid, 1.0)
+        k = kept.long()
+        return i0[k], i1[k], i2[k], corres_idx0, corres_idx1, idx1_2nd, kept_norm
     _, _, norm, num_bb = match_ratio(fcgf_feats0, fcgf_feats1, corres_idx1, idx1_2nd, rev)
     kept, kept_norm, _ = gpf_select(_dev(xyz0, "xyz0")[corres_idx0], norm, num_bb, args.GPF_grid_wid, args.GPF_factor)
     k = kept.long()
