@@ -833,6 +833,158 @@ int32_t pdsc_teaser_solve(const float *src, const float *tgt, int32_t N, double 
                           float *labels /* may be NULL */, void *workspace, size_t workspace_bytes,
                           pdsc_stream_t stream);
 
+/* ------------------------------------------------------ f10 GC-RANSAC ------
+ * The fork's --algo GC (algorithms/GC_RANSAC.py:8-50 from algorithms/FR.py:70-87;
+ * baseline_scripts/baseline_3DMatch.py:101-123): Graph-Cut RANSAC (Barath &
+ * Matas, CVPR 2018) for a rigid motion, in the configuration the fork runs:
+ * neighborhood 0 (the grid graph), neighborhood_size 20, the uniform sampler.
+ * The reference calls the x86 library pygcransac, which is neither installed nor
+ * in the reference tree: the definitions below are written from the published
+ * algorithm and ARE the contract; parity with the library itself is unpinned
+ * (as parity with open3d is for f6).  Nothing here synchronises the stream or
+ * allocates; every argument is checked on the host before any device work; all
+ * arithmetic is fp64 without contraction in a fixed order and only integer
+ * atomics are used: two calls are bitwise equal.  Row i of src [N,3] corresponds
+ * to row i of tgt [N,3] (fp32, finite).
+ *
+ * pdsc_gc_grid: the neighbourhood.  The six axes a = 0 .. 5 are (sx, sy, sz, tx,
+ * ty, tz); for an axis with column minimum m and maximum M (fp32) the cell
+ * coordinate of x is c = min(G - 1, (int)floor((G * (x - m)) / (M - m))) in fp64
+ * from the fp32 values, in that operation order, and c = 0 where M == m; key =
+ * sum_a c_a G^(5 - a) as an unsigned 64-bit value.  Two rows are neighbours iff
+ * their keys are equal: the graph is a disjoint union of cliques, the cells.
+ *   order [N]             the rows sorted by (key, row);
+ *   cell_start [N + 1]    capacity; cell k is order[cell_start[k] ..
+ *                         cell_start[k + 1]), k < n_cells, cells by ascending key;
+ *   cell_of [N]           the cell of each row;
+ *   n_cells               device int32.
+ * 1 <= G <= 1024 and 1 <= N (else PDSC_ERR_ARG), N <= 262144
+ * (PDSC_ERR_UNSUPPORTED; pdsc_gpf_select's bound).  One workgroup: the sort is a
+ * bitonic network, in LDS up to 2048 rows and in global memory above.
+ *
+ * pdsc_gc_label: the graph-cut labelling of the rows under a pose (device
+ * double[16], row-major 4x4), threshold eps > 0 and spatial_coherence_weight
+ * lambda in [0, 1].  d2_p = |R s_p + t - t_p|^2 as f6's Score; K_p = exp(-(d2_p
+ * / (2 eps^2))), 2 eps^2 = 2.0 * (eps * eps).  The energy of a labelling L is
+ *   sum_p (1 - lambda) (L_p == 1 ? 1 - K_p : K_p)
+ *   + lambda sum over unordered pairs p < q of one cell of
+ *       1 if L_p != L_q, (K_p + K_q) / 2 if both are 0, 1 - (K_p + K_q) / 2 if
+ *       both are 1
+ * (the paper's, with the implementation's convex weighting).  Inside a cell every
+ * pair has the same weight (E(0,1) + E(1,0) - E(0,0) - E(1,1) = lambda), so the
+ * minimum over all labellings -- what the library's max-flow computes on this
+ * graph -- is found per cell of n rows exactly:
+ *   sort the rows by (d2, row) ascending; P(m) = K of the first m rows summed
+ *   sequentially in that order from 0.0, S = P(n); with m, n as doubles
+ *     u = (m - 2 P(m)) + S
+ *     a = m (n - m);  b = (((n - m) - 1) 0.5) (S - P(m))
+ *     c = (m (m - 1)) 0.5;  d = ((m - 1) 0.5) P(m)
+ *     E(m) = (1 - lambda) u + lambda (((a + b) + c) - d)
+ *   m* = argmin of E over m = 0 .. n, ties to the lower m (with ties to the higher
+ *   m, lambda = 1 would label every singleton an inlier); the first m* rows of
+ *   the cell get label 1.
+ * labels [N] fp32 0/1; count (device int32) = the rows labelled 1.  Debug (a HOST
+ * struct of device pointers, any may be NULL): d2 [N]; per cell m_star, energy =
+ * E(m*) and energy_gap = the second-lowest of the n + 1 values minus the lowest.
+ * Correct for every cell size 1 .. N (one far outlier stretches an axis and can
+ * put almost every row in one cell).  The split by cell size: up to
+ * pdsc_gc_cell_bound(0) = 64 rows one wavefront sorts in registers; up to
+ * pdsc_gc_cell_bound(1) = 1024 rows one workgroup sorts in LDS; above, the
+ * workgroup sorts in the cell's segment of the workspace.  The energies and the
+ * argmin are parallel, the prefix sum is sequential: a cell of n rows costs n
+ * dependent additions and O(n log^2 n) compares.
+ *
+ * pdsc_gc_ransac: the solver; H = max_iteration hypotheses h = 0 .. H - 1.
+ *   Sampling, Estimate   f6's with ransac_n = 3: the same draw formula and seed,
+ *               the same Kabsch; a repeated index gives status (count) -1.
+ *   Score       MSAC: an inlier has d2 < eps^2 (eps^2 = eps * eps); score = sum
+ *               over the inliers of (1 - d2 / eps^2) and count = the inliers, in
+ *               f6's order: chunks of 256 rows, each summed in row order from
+ *               0.0, then the chunks in order from 0.0.
+ *   Rounds      pdsc_gc_ransac_round() = pdsc_ransac_round() hypotheses per round
+ *               (f6's size: no measurement argued for another; it is part of the
+ *               result's definition).  The round's best: the higher score, then
+ *               the lower h.  If its score is higher than the so-far-best's (none
+ *               yet: -1) it is the candidate, and with local_optimization != 0
+ *               the LO runs from it (lo_runs += 1), theta = the candidate, for at
+ *               most 10 steps (lo_steps += 1 for every step that labels):
+ *                 1. label under theta as above; stop if fewer than 3 rows get 1;
+ *                 2. theta' = one unit-weight fp64 Kabsch over the labelled rows
+ *                    (f6's refit over that row set);
+ *                 3. if score(theta') > score(theta): theta = theta' (with its
+ *                    score and count) and continue; otherwise stop.
+ *               theta after the LO has the higher score of the round's best and
+ *               the LO's result; it becomes the so-far-best (best stays the h of
+ *               the round's best).  A round whose best does not beat the
+ *               so-far-best changes nothing.
+ *   Stop        f6's rule at round granularity with exponent 3 and f = the
+ *               so-far-best's count / N: after round r, when confidence < 1 and
+ *               count > 0, stop if count = N or (r + 1) round >= log(1 -
+ *               confidence) / log(1 - f f f).
+ *   Result      labels [N] = 1 where d2 < eps^2 under the so-far-best, n_inliers
+ *               their number, score its score; trans = pdsc_refit_inliers' fit of
+ *               that pose over the same rows (the same code: bitwise equal; the
+ *               pose itself with fewer than 3 inliers); trans_f32 = (float)
+ *               trans.  n_cells = the grid's (0 with local_optimization == 0,
+ *               which builds no grid and ignores lambda and G beyond the argument
+ *               check).  Without a valid hypothesis: the identity, zeros, best -1.
+ *   Device loop as f6: nothing synchronises, every round and every LO step is
+ *               enqueued up front, work after the stop (and LO steps that have
+ *               nothing to do) returns at entry.
+ *   Deviations from the library: the LO runs at round granularity, not at each
+ *               new best; its refit is a least-squares fit over all labelled rows
+ *               where the library draws inner samples of 7 x the minimal size;
+ *               SPRT pre-emption is left out (it only saves CPU time), and so are
+ *               the fork's edge-length pre-emption (its C++ is not in the tree),
+ *               PROSAC and the FLANN neighbourhood.
+ *   Errors      PDSC_ERR_ARG for N < 3, max_iteration < 1, threshold <= 0 or not
+ *               finite, confidence outside (0, 1], lambda outside [0, 1], G
+ *               outside [1, 1024], null src / tgt / workspace, a workspace that
+ *               is too small; PDSC_ERR_UNSUPPORTED for N > 262144.
+ * Debug rows (H = max_iteration) as f6's: count -3 for hypotheses never drawn,
+ * samples for every drawn one, score / trans only for valid ones.             */
+typedef struct pdsc_gc_label_debug {  /* HOST struct of device pointers, any may be NULL */
+    double  *d2;                      /* [N] */
+    int32_t *m_star;                  /* [n_cells] (capacity N) */
+    double  *energy;                  /* [n_cells] */
+    double  *energy_gap;              /* [n_cells] */
+} pdsc_gc_label_debug;
+typedef struct pdsc_gc_ransac_result { /* device memory, written by the call */
+    double  trans[16];                /* fp64 row-major, source -> target */
+    double  score;                    /* the so-far-best's MSAC score */
+    int32_t n_inliers;
+    int32_t iterations;               /* hypotheses drawn: a multiple of the round, or max_iteration */
+    int32_t best;                     /* h of the round's best the result descends from, -1: none valid */
+    int32_t lo_runs, lo_steps;
+    int32_t n_cells;
+} pdsc_gc_ransac_result;
+typedef struct pdsc_gc_ransac_debug { /* any member may be NULL; H = max_iteration */
+    int32_t *samples;                 /* [H,3] */
+    int32_t *count;                   /* [H]: inliers, -1 repeated index, -3 not drawn */
+    double  *score;                   /* [H] */
+    double  *trans;                   /* [H,16] */
+} pdsc_gc_ransac_debug;
+int32_t pdsc_gc_cell_bound(int32_t which);  /* 0: rows of a wavefront cell, 1: of an LDS cell, else 0 */
+size_t  pdsc_gc_grid_workspace_bytes(int32_t N);
+int32_t pdsc_gc_grid(const float *src, const float *tgt, int32_t N, int32_t G, int32_t *order, int32_t *cell_start,
+                     int32_t *cell_of, int32_t *n_cells, void *workspace, size_t workspace_bytes,
+                     pdsc_stream_t stream);
+size_t  pdsc_gc_label_workspace_bytes(int32_t N);
+int32_t pdsc_gc_label(const double *pose, const float *src, const float *tgt, int32_t N, const int32_t *order,
+                      const int32_t *cell_start, const int32_t *n_cells, double threshold,
+                      double spatial_coherence_weight, float *labels, int32_t *count,
+                      const pdsc_gc_label_debug *debug /* may be NULL */, void *workspace, size_t workspace_bytes,
+                      pdsc_stream_t stream);
+int32_t pdsc_gc_ransac_round(void);
+size_t  pdsc_gc_ransac_workspace_bytes(int32_t N);
+int32_t pdsc_gc_ransac(const float *src, const float *tgt, int32_t N, double threshold,
+                       double spatial_coherence_weight, int32_t neighborhood_size, int32_t max_iteration,
+                       double confidence /* 1.0: never stop early */, uint64_t seed, int32_t local_optimization,
+                       float *trans_f32 /* may be NULL */, float *labels /* [N] 0/1, may be NULL */,
+                       pdsc_gc_ransac_result *result /* may be NULL */,
+                       const pdsc_gc_ransac_debug *debug /* HOST struct of device pointers, may be NULL */,
+                       void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+
 /* ----------------------------------------------- full testing forward ------
  * PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197)
  * for B independent pairs: compat -> encoder -> classifier -> seeds -> kNN ->

@@ -8,7 +8,9 @@ baseline and ``--solver RANSAC``); ``pointdsc_amd.matching`` / ``pointdsc_amd.fr
 are the fork's correspondence filters (MFR, GPF) and its filtered RANSAC ``FR``;
 ``pointdsc_amd.baselines`` holds the baselines ``SM``, ``RANSAC`` and ``PMC``
 (consistency graph + maximum clique); ``pointdsc_amd.teaser`` is the fork's
-``TEASER`` (graph, clique, GNC-TLS rotation, TLS translation); the C ABI is ``include/pdsc.h`` /
+``TEASER`` (graph, clique, GNC-TLS rotation, TLS translation);
+``pointdsc_amd.gc_ransac`` is its ``GC`` (GC-RANSAC on the grid neighbourhood, the
+exact per-cell graph cut; ``GCRANSAC`` is the baseline); the C ABI is ``include/pdsc.h`` /
 ``pointdsc_amd/libpdsc.so``.
 """
 __version__ = "0.1.0"
@@ -20,14 +22,19 @@ _MATCHING = ("find_nn", "find_2nn", "nn_to_mutual", "mark_best_buddies", "calc_d
 _FR = ("FR",)
 _PMC = ("PMC",)
 _TEASER = ("TEASER",)
-__all__ = [*_ICP, *_RANSAC, *_MATCHING, *_FR, *_PMC, *_TEASER]
+_GC = ("GC_RANSAC", "gc_grid", "gc_label")  # the solver itself: pointdsc_amd.gc_ransac.gc_ransac (the module's name)
+_GCRANSAC = ("GCRANSAC",)
+__all__ = [*_ICP, *_RANSAC, *_MATCHING, *_FR, *_PMC, *_TEASER, *_GC, *_GCRANSAC]
 
 
-def __getattr__(name):  # the ICP / RANSAC / FR / PMC / TEASER entry points, without importing torch on `import pointdsc_amd`
+def __getattr__(name):  # the ICP / RANSAC / FR / PMC / TEASER / GC entry points, without importing torch on `import pointdsc_amd`
     if name in _TEASER:
         from . import teaser
         return getattr(teaser, name)
-    if name in _PMC:
+    if name in _GC:
+        from . import gc_ransac
+        return getattr(gc_ransac, name)
+    if name in _PMC or name in _GCRANSAC:
         from . import baselines
         return getattr(baselines, name)
     if name in _MATCHING:

@@ -83,6 +83,22 @@ class PdscTeaserResult(ctypes.Structure):
                 ("n_translation_inliers", c_int32), ("reserved", c_int32)]
 
 
+class PdscGcLabelDebug(ctypes.Structure):
+    """``struct pdsc_gc_label_debug`` (include/pdsc.h): optional outputs of pdsc_gc_label."""
+    _fields_ = [("d2", vp), ("m_star", vp), ("energy", vp), ("energy_gap", vp)]
+
+
+class PdscGcRansacResult(ctypes.Structure):
+    """``struct pdsc_gc_ransac_result`` (include/pdsc.h): 160 bytes of device memory."""
+    _fields_ = [("trans", c_double * 16), ("score", c_double), ("n_inliers", c_int32), ("iterations", c_int32),
+                ("best", c_int32), ("lo_runs", c_int32), ("lo_steps", c_int32), ("n_cells", c_int32)]
+
+
+class PdscGcRansacDebug(ctypes.Structure):
+    """``struct pdsc_gc_ransac_debug`` (include/pdsc.h): optional per-hypothesis outputs."""
+    _fields_ = [("samples", vp), ("count", vp), ("score", vp), ("trans", vp)]
+
+
 # enum pdsc_edge_mode (include/pdsc.h)
 EDGE_MODES = {"squared": 0, "length": 1}
 
@@ -175,6 +191,16 @@ _PROTOS = {
     "pdsc_teaser_solve_workspace_bytes": (c_size_t, [c_int32]),
     "pdsc_teaser_solve": (c_int32, [vp, vp, c_int32, c_double, c_double, c_int32, c_double, ctypes.c_int64, vp, vp,
                                     vp, vp, c_size_t, vp]),
+    "pdsc_gc_cell_bound": (c_int32, [c_int32]),
+    "pdsc_gc_grid_workspace_bytes": (c_size_t, [c_int32]),
+    "pdsc_gc_grid": (c_int32, [vp, vp, c_int32, c_int32, vp, vp, vp, vp, vp, c_size_t, vp]),
+    "pdsc_gc_label_workspace_bytes": (c_size_t, [c_int32]),
+    "pdsc_gc_label": (c_int32, [vp, vp, vp, c_int32, vp, vp, vp, c_double, c_double, vp, vp,
+                                ctypes.POINTER(PdscGcLabelDebug), vp, c_size_t, vp]),
+    "pdsc_gc_ransac_round": (c_int32, []),
+    "pdsc_gc_ransac_workspace_bytes": (c_size_t, [c_int32]),
+    "pdsc_gc_ransac": (c_int32, [vp, vp, c_int32, c_double, c_double, c_int32, c_int32, c_double, ctypes.c_uint64,
+                                 c_int32, vp, vp, vp, ctypes.POINTER(PdscGcRansacDebug), vp, c_size_t, vp]),
     "pdsc_forward_training_workspace_bytes": (c_size_t, [CFG, c_int32, c_int32]),
     "pdsc_range_status": (c_int32, [vp, c_int32, ctypes.POINTER(c_int32), vp]),
     "pdsc_range_poll": (c_int32, [vp, c_int32, vp]),

@@ -1,4 +1,4 @@
-"""The reference's baselines on the GPU: SM, RANSAC, PMC.
+"""The reference's baselines on the GPU: SM, RANSAC, PMC, GCRANSAC.
 
 ``SM(corr, src_keypts, tgt_keypts, ...)`` mirrors
 baseline_scripts/baseline_3DMatch.py:19-53 -- same inputs (``corr`` is the
@@ -80,6 +80,29 @@ def PMC(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, mode: str 
     pred_labels = labels[None]
     pred_trans = rigid_transform_3d(src, tgt, pred_labels)
     return (pred_trans, pred_labels, CliqueInfo(result)) if return_info else (pred_trans, pred_labels)
+
+
+def GCRANSAC(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, max_iteration: int = 1000, seed: int = 0):
+    """baseline_scripts/baseline_3DMatch.py:101-123: GC-RANSAC over every
+    correspondence (``corr`` is accepted for the baselines' common signature and
+    not read, as there) with spatial_coherence_weight 0.1 and conf 0.99999999,
+    ``args.inlier_threshold`` and ``args.max_iteration`` passed as keywords.  Same
+    outputs as ``SM``: ``(pred_trans [1,4,4], pred_labels [1,N])``; an empty mask
+    gives the identity.  Runs on pointdsc_amd/csrc/gc_ransac.hip (pdsc_gc_ransac,
+    include/pdsc.h f10: the algorithm restated, parity with pygcransac itself is
+    unpinned; its SPRT pre-emption is left out); ``seed`` fixes the draws.  No CPU
+    fallback."""
+    from .gc_ransac import gc_ransac
+    src, tgt = _dev(src_keypts, "src_keypts"), _dev(tgt_keypts, "tgt_keypts")
+    assert src.shape[0] == 1, "GCRANSAC: bs = 1 (baseline_3DMatch.py:104-105)"
+    N = src.shape[1]
+    if src.shape != (1, N, 3) or tgt.shape != (1, N, 3):
+        raise ValueError(f"shapes {tuple(src.shape)} {tuple(tgt.shape)}")
+    res = gc_ransac(src[0], tgt[0], inlier_threshold, 0.1, max_iteration, 0.99999999, seed)
+    pred_trans = res.transformation_f32[None]
+    if res.n_inliers == 0:
+        pred_trans = torch.eye(4, dtype=torch.float32, device=src.device)[None]
+    return pred_trans, res.labels[None]
 
 
 def sm_matvec(M, v):

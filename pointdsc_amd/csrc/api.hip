@@ -1421,6 +1421,75 @@ int32_t pdsc_teaser_solve(const float *src, const float *tgt, int32_t N, double 
     return PDSC_OK;
 }
 
+// ------------------------------------------------------------ f10 GC-RANSAC
+int32_t pdsc_gc_cell_bound(int32_t which) { return which == 0 ? GC_WAVE_CELL : which == 1 ? GC_LDS_CELL : 0; }
+
+int32_t pdsc_gc_ransac_round(void) { return RANSAC_ROUND; }
+
+static int32_t check_gc_rows(int32_t N, int32_t least) {
+    if (N < least) return fail(PDSC_ERR_ARG, "N=%d (need >= %d)", N, least);
+    if (N > GC_MAX_ROWS) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, GC_MAX_ROWS);
+    return PDSC_OK;
+}
+
+static int32_t check_gc_grid_size(int32_t G) {
+    if (G < 1 || G > GC_MAX_GRID) return fail(PDSC_ERR_ARG, "neighborhood_size G=%d not in [1, %d]", G, GC_MAX_GRID);
+    return PDSC_OK;
+}
+
+static int32_t check_gc_model(double threshold, double lambda) {
+    if (!(threshold > 0.0) || !std::isfinite(threshold))
+        return fail(PDSC_ERR_ARG, "threshold %g must be > 0 and finite", threshold);
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(PDSC_ERR_ARG, "spatial_coherence_weight %g not in [0, 1]", lambda);
+    return PDSC_OK;
+}
+
+size_t pdsc_gc_grid_workspace_bytes(int32_t N) { return N < 1 || N > GC_MAX_ROWS ? 0 : gc_grid_workspace_bytes(N); }
+
+int32_t pdsc_gc_grid(const float *src, const float *tgt, int32_t N, int32_t G, int32_t *order, int32_t *cell_start,
+                     int32_t *cell_of, int32_t *n_cells, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_gc_rows(N, 1));
+    RET_IF(check_gc_grid_size(G));
+    if (!src || !tgt || !order || !cell_start || !cell_of || !n_cells || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_gc_grid_workspace_bytes(N)));
+    HIPCHK(launch_gc_grid(src, tgt, N, G, order, cell_start, cell_of, n_cells, ws, S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_gc_label_workspace_bytes(int32_t N) { return N < 1 || N > GC_MAX_ROWS ? 0 : gc_label_workspace_bytes(N); }
+
+int32_t pdsc_gc_label(const double *pose, const float *src, const float *tgt, int32_t N, const int32_t *order,
+                      const int32_t *cell_start, const int32_t *n_cells, double threshold, double lambda, float *labels,
+                      int32_t *count, const pdsc_gc_label_debug *debug, void *ws, size_t ws_bytes,
+                      pdsc_stream_t stream) {
+    RET_IF(check_gc_rows(N, 1));
+    RET_IF(check_gc_model(threshold, lambda));
+    if (!pose || !src || !tgt || !order || !cell_start || !n_cells || !labels || !count || !ws)
+        return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_gc_label_workspace_bytes(N)));
+    HIPCHK(launch_gc_label(pose, src, tgt, N, order, cell_start, n_cells, threshold, lambda, labels, count, debug, ws,
+                           S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_gc_ransac_workspace_bytes(int32_t N) { return N < 3 || N > GC_MAX_ROWS ? 0 : gc_ransac_workspace_bytes(N); }
+
+int32_t pdsc_gc_ransac(const float *src, const float *tgt, int32_t N, double threshold, double lambda, int32_t G,
+                       int32_t max_iteration, double confidence, uint64_t seed, int32_t local_optimization,
+                       float *trans_f32, float *labels, pdsc_gc_ransac_result *result,
+                       const pdsc_gc_ransac_debug *debug, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_gc_rows(N, 3));
+    if (max_iteration < 1) return fail(PDSC_ERR_ARG, "max_iteration=%d (need >= 1)", max_iteration);
+    RET_IF(check_gc_model(threshold, lambda));
+    if (!(confidence > 0.0 && confidence <= 1.0)) return fail(PDSC_ERR_ARG, "confidence %g not in (0, 1]", confidence);
+    RET_IF(check_gc_grid_size(G));
+    if (!src || !tgt || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_gc_ransac_workspace_bytes(N)));
+    HIPCHK(launch_gc_ransac(src, tgt, N, threshold, lambda, G, max_iteration, confidence, seed,
+                            local_optimization ? 1 : 0, trans_f32, labels, result, debug, ws, S_(stream)));
+    return PDSC_OK;
+}
+
 // ------------------------------------------------- f1 correspondence construction
 size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
     return align_bytes((size_t)Ns * 8) + align_bytes((size_t)Nt * 8);

@@ -342,6 +342,24 @@ hipError_t launch_ransac(const float *src, const float *tgt, int N, double max_d
 hipError_t launch_refit_inliers(const double *pose, const float *src, const float *tgt, int N, double radius,
                                 double *trans, float *trans_f32, int *count, float *labels, hipStream_t s);
 
+// GC-RANSAC (gc_ransac.hip, f10): the grid neighbourhood, the exact per-cell graph cut, the solver
+constexpr int GC_MAX_ROWS = 1 << 18;  // as GPF_MAX_ROWS; also the LDS chunk rows of the one-pose scorer
+constexpr int GC_MAX_GRID = 1024;     // cells per axis: 6 axes of 10 bits in the 64-bit key
+constexpr int GC_WAVE_CELL = 64;      // cells up to this many rows: one wave, a row per lane
+constexpr int GC_LDS_CELL = 1024;     // up to this many: one workgroup in LDS; above: its global scratch
+size_t gc_grid_workspace_bytes(int N);
+hipError_t launch_gc_grid(const float *src, const float *tgt, int N, int G, int *order, int *cell_start, int *cell_of,
+                          int *n_cells, void *ws, hipStream_t s);
+size_t gc_label_workspace_bytes(int N);
+hipError_t launch_gc_label(const double *pose, const float *src, const float *tgt, int N, const int *order,
+                           const int *cell_start, const int *n_cells, double threshold, double lambda, float *labels,
+                           int *count, const pdsc_gc_label_debug *debug, void *ws, hipStream_t s);
+size_t gc_ransac_workspace_bytes(int N);
+// Enqueues the grid (lo != 0), every round with its LO steps and the finish; H = max_iteration.
+hipError_t launch_gc_ransac(const float *src, const float *tgt, int N, double threshold, double lambda, int G, int H,
+                            double confidence, unsigned long long seed, int lo, float *trans_f32, float *labels,
+                            pdsc_gc_ransac_result *res, const pdsc_gc_ransac_debug *debug, void *ws, hipStream_t s);
+
 // filtered-RANSAC front end (match_filter.hip, f7)
 constexpr int NN2_MAX_SPLIT = 16;  // column splits per row stripe the workspace is sized for
 int nn2_default_split(int Na, int Nb);
