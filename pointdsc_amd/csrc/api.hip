@@ -13,6 +13,7 @@
 
 #include "launch_plan.hpp"
 #include "pdsc_internal.hpp"
+#include "workspace.hpp"
 
 using namespace pdsc;
 
@@ -51,18 +52,6 @@ int fail(int code, const char *fmt, ...) {
     } while (0)
 
 hipStream_t S_(pdsc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
-// Bump allocator over a caller workspace (256-B aligned slices).
-struct Carve {
-    char *base;
-    size_t off = 0;
-    explicit Carve(void *p) : base(static_cast<char *>(p)) {}
-    template <typename T> T *take(size_t n) {
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += align_bytes(n * sizeof(T));
-        return p;
-    }
-};
 
 int check_cfg(const pdsc_config *cfg) {
     if (!cfg) return fail(PDSC_ERR_ARG, "cfg is NULL");
@@ -702,8 +691,21 @@ int run_seed_knn(const TailPlan &tp, const float *normed, const _Float16 *normed
     return PDSC_OK;
 }
 
+// the seed rows' distances [B][S][N] and the split normed copy [B][N][2][CH]
+struct SeedKnnBufs {
+    float *dist;
+    _Float16 *ns;
+};
+static void bind_seed_knn(Carve &c, int B, int N, int S, SeedKnnBufs &W) {
+    W.dist = c.take<float>((size_t)B * S * N);
+    W.ns = c.take<_Float16>((size_t)B * N * 2 * CH);
+}
+
 size_t pdsc_seed_knn_workspace_bytes(int32_t B, int32_t N, int32_t S) {
-    return align_bytes((size_t)B * S * N * sizeof(float)) + align_bytes((size_t)B * N * 2 * CH * sizeof(_Float16));
+    Carve c(nullptr);
+    SeedKnnBufs W;
+    bind_seed_knn(c, B, N, S, W);
+    return c.off;
 }
 
 int32_t pdsc_seed_knn(const float *normed, const int32_t *seeds, int32_t B, int32_t N, int32_t C,
@@ -717,11 +719,11 @@ int32_t pdsc_seed_knn(const float *normed, const int32_t *seeds, int32_t B, int3
     RET_IF(need_ws(ws_bytes, pdsc_seed_knn_workspace_bytes(B, N, S)));
     hipStream_t s = S_(stream);
     Carve c(ws);
-    float *dist = c.take<float>((size_t)B * S * N);
-    _Float16 *ns = c.take<_Float16>((size_t)B * N * 2 * CH);
+    SeedKnnBufs W;
+    bind_seed_knn(c, B, N, S, W);
     const bool f32 = precision == PDSC_PRECISION_F32;
-    if (!f32) HIPCHK(launch_split_rows(normed, (size_t)B * N, ns, s));
-    return run_seed_knn(plan_tail(B, N, S), normed, ns, f32, seeds, B, N, S, k, dist, knn, s);
+    if (!f32) HIPCHK(launch_split_rows(normed, (size_t)B * N, W.ns, s));
+    return run_seed_knn(plan_tail(B, N, S), normed, W.ns, f32, seeds, B, N, S, k, W.dist, knn, s);
 }
 
 // ----------------------------------------------------------------- a7-a8
@@ -759,8 +761,12 @@ int32_t pdsc_rigid_transform_3d(const float *A, const float *Bp, const float *w,
 }
 
 // ------------------------------------------------------------------- a10
+static float *bind_hypothesis_sums(Carve &c, int B, int S) { return c.take<float>((size_t)B * S * 15); }
+
 size_t pdsc_seed_hypotheses_workspace_bytes(int32_t B, int32_t S) {
-    return align_bytes((size_t)B * S * 15 * sizeof(float));
+    Carve c(nullptr);
+    bind_hypothesis_sums(c, B, S);
+    return c.off;
 }
 
 int32_t pdsc_seed_hypotheses(const float *src, const float *tgt, const int32_t *knn, const float *weights,
@@ -778,8 +784,9 @@ int32_t pdsc_seed_hypotheses(const float *src, const float *tgt, const int32_t *
     int *counts = reinterpret_cast<int *>(fitness);
     if (!ws || ws_bytes < pdsc_seed_hypotheses_workspace_bytes(B, S))
         return fail(PDSC_ERR_ARG, "workspace too small");
+    Carve c(ws);
     HIPCHK(launch_hypotheses(plan_tail(B, N, S), src, tgt, knn, weights, B, N, S, k, tau, seed_trans, counts,
-                             static_cast<float *>(ws), s));
+                             bind_hypothesis_sums(c, B, S), s));
     HIPCHK(launch_select_best(src, tgt, seed_trans, counts, B, N, S, tau, fitness, best, trans, labels, s));
     return PDSC_OK;
 }
@@ -1075,8 +1082,13 @@ int32_t pdsc_range_poll(const void *ws, int32_t B, pdsc_stream_t stream) {
     return PDSC_OK;
 }
 
+static double *bind_sm_loss(Carve &c, int B, int N) { return c.take<double>(sm_loss_partial_doubles(B, N)); }
+
 size_t pdsc_spectral_matching_loss_workspace_bytes(int32_t B, int32_t N) {
-    return (B < 1 || N < 1) ? 0 : align_bytes(sm_loss_partial_doubles(B, N) * sizeof(double));
+    if (B < 1 || N < 1) return 0;
+    Carve c(nullptr);
+    bind_sm_loss(c, B, N);
+    return c.off;
 }
 
 int32_t pdsc_spectral_matching_loss(const float *M, const float *gt_labels, int32_t B, int32_t N, int32_t balanced,
@@ -1084,7 +1096,8 @@ int32_t pdsc_spectral_matching_loss(const float *M, const float *gt_labels, int3
     if (!M || !gt_labels || !loss || !ws) return fail(PDSC_ERR_ARG, "null pointer");
     if (B < 1 || N < 1) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
     RET_IF(need_ws(ws_bytes, pdsc_spectral_matching_loss_workspace_bytes(B, N)));
-    HIPCHK(launch_sm_loss(M, gt_labels, B, N, balanced, static_cast<double *>(ws), loss, S_(stream)));
+    Carve c(ws);
+    HIPCHK(launch_sm_loss(M, gt_labels, B, N, balanced, bind_sm_loss(c, B, N), loss, S_(stream)));
     return PDSC_OK;
 }
 
@@ -1122,15 +1135,31 @@ int32_t pdsc_radius_knn(const float *pts, int32_t n, float radius, int32_t max_n
     if (!nbr || !count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
     RET_IF(need_ws(ws_bytes, pdsc_radius_knn_workspace_bytes(n)));
     hipStream_t s = S_(stream);
+    Carve c(ws);
     GridBufs G;
-    HIPCHK(build_grid(pts, n, radius, 0.0, ws, G, s));
+    bind_grid(c, n, G);
+    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
     HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, nbr, dist2, count, s));
     return grid_status(G, s);
 }
 
+// the grid, then the neighbour lists [n][max_nn] and their lengths [n]
+struct NormalsBufs {
+    GridBufs grid;
+    int *nbr, *cnt;
+};
+static void bind_normals(Carve &c, int n, int max_nn, NormalsBufs &W) {
+    bind_grid(c, n, W.grid);
+    W.nbr = c.take<int>((size_t)n * max_nn);
+    W.cnt = c.take<int>((size_t)n);
+}
+
 size_t pdsc_estimate_normals_workspace_bytes(int32_t n, int32_t max_nn) {
     if (n < 1 || max_nn < 1) return 0;
-    return grid_workspace_bytes(n) + align_bytes((size_t)n * max_nn * sizeof(int)) + align_bytes((size_t)n * sizeof(int));
+    Carve c(nullptr);
+    NormalsBufs W;
+    bind_normals(c, n, max_nn, W);
+    return c.off;
 }
 
 int32_t pdsc_estimate_normals(const float *pts, int32_t n, float radius, int32_t max_nn, int32_t orient,
@@ -1142,13 +1171,13 @@ int32_t pdsc_estimate_normals(const float *pts, int32_t n, float radius, int32_t
     if (orient == PDSC_NORMALS_VIEWPOINT && !viewpoint) return fail(PDSC_ERR_ARG, "PDSC_NORMALS_VIEWPOINT needs a viewpoint");
     RET_IF(need_ws(ws_bytes, pdsc_estimate_normals_workspace_bytes(n, max_nn)));
     hipStream_t s = S_(stream);
-    char *w = static_cast<char *>(ws);
-    int *nbr = reinterpret_cast<int *>(w + grid_workspace_bytes(n));
-    int *cnt = reinterpret_cast<int *>(reinterpret_cast<char *>(nbr) + align_bytes((size_t)n * max_nn * sizeof(int)));
-    GridBufs G;
-    HIPCHK(build_grid(pts, n, radius, 0.0, ws, G, s));
-    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, nbr, nullptr, cnt, s));
-    HIPCHK(launch_normals(pts, n, nbr, cnt, max_nn, G, orient, viewpoint, normals, s));
+    Carve c(ws);
+    NormalsBufs W;
+    bind_normals(c, n, max_nn, W);
+    const GridBufs &G = W.grid;
+    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
+    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, W.nbr, nullptr, W.cnt, s));
+    HIPCHK(launch_normals(pts, n, W.nbr, W.cnt, max_nn, G, orient, viewpoint, normals, s));
     return grid_status(G, s);
 }
 
@@ -1161,17 +1190,34 @@ int32_t pdsc_voxel_down_sample(const float *pts, const float *normals, int32_t n
     if (!out_pts || !out_count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
     RET_IF(need_ws(ws_bytes, pdsc_voxel_down_sample_workspace_bytes(n)));
     hipStream_t s = S_(stream);
+    Carve c(ws);
     GridBufs G;
-    HIPCHK(build_grid(pts, n, voxel_size, 0.5 * (double)voxel_size, ws, G, s));
+    bind_grid(c, n, G);
+    HIPCHK(build_grid(pts, n, voxel_size, 0.5 * (double)voxel_size, G, s));
     HIPCHK(launch_voxel_reduce(pts, normals, n, G, out_pts, out_normals, out_count, s));
     return grid_status(G, s);
 }
 
+// the grid, then the neighbour lists and their d^2 [n][max_nn], the lengths [n] and the SPFH rows [n][33]
+struct FpfhBufs {
+    GridBufs grid;
+    int *nbr, *cnt;
+    double *d2, *spfh;
+};
+static void bind_fpfh(Carve &c, int n, int max_nn, FpfhBufs &W) {
+    bind_grid(c, n, W.grid);
+    W.nbr = c.take<int>((size_t)n * max_nn);
+    W.d2 = c.take<double>((size_t)n * max_nn);
+    W.cnt = c.take<int>((size_t)n);
+    W.spfh = c.take<double>((size_t)n * 33);
+}
+
 size_t pdsc_compute_fpfh_workspace_bytes(int32_t n, int32_t max_nn) {
     if (n < 1 || max_nn < 1) return 0;
-    return grid_workspace_bytes(n) + align_bytes((size_t)n * max_nn * sizeof(int)) +
-           align_bytes((size_t)n * max_nn * sizeof(double)) + align_bytes((size_t)n * sizeof(int)) +
-           align_bytes((size_t)n * 33 * sizeof(double));
+    Carve c(nullptr);
+    FpfhBufs W;
+    bind_fpfh(c, n, max_nn, W);
+    return c.off;
 }
 
 int32_t pdsc_compute_fpfh(const float *pts, const float *normals, int32_t n, float radius, int32_t max_nn,
@@ -1180,18 +1226,13 @@ int32_t pdsc_compute_fpfh(const float *pts, const float *normals, int32_t n, flo
     if (!normals || !fpfh || !ws) return fail(PDSC_ERR_ARG, "null pointer");
     RET_IF(need_ws(ws_bytes, pdsc_compute_fpfh_workspace_bytes(n, max_nn)));
     hipStream_t s = S_(stream);
-    char *w = static_cast<char *>(ws) + grid_workspace_bytes(n);
-    int *nbr = reinterpret_cast<int *>(w);
-    w += align_bytes((size_t)n * max_nn * sizeof(int));
-    double *d2 = reinterpret_cast<double *>(w);
-    w += align_bytes((size_t)n * max_nn * sizeof(double));
-    int *cnt = reinterpret_cast<int *>(w);
-    w += align_bytes((size_t)n * sizeof(int));
-    double *spfh = reinterpret_cast<double *>(w);
-    GridBufs G;
-    HIPCHK(build_grid(pts, n, radius, 0.0, ws, G, s));
-    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, nbr, d2, cnt, s));
-    HIPCHK(launch_fpfh(pts, normals, n, nbr, cnt, d2, max_nn, spfh, fpfh, fpfh_normalized, s));
+    Carve c(ws);
+    FpfhBufs W;
+    bind_fpfh(c, n, max_nn, W);
+    const GridBufs &G = W.grid;
+    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
+    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, W.nbr, W.d2, W.cnt, s));
+    HIPCHK(launch_fpfh(pts, normals, n, W.nbr, W.cnt, W.d2, max_nn, W.spfh, fpfh, fpfh_normalized, s));
     return grid_status(G, s);
 }
 
@@ -1491,10 +1532,22 @@ int32_t pdsc_gc_ransac(const float *src, const float *tgt, int32_t N, double thr
 }
 
 // ------------------------------------------------- f1 correspondence construction
-size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
-    return align_bytes((size_t)Ns * 8) + align_bytes((size_t)Nt * 8);
+// the packed (distance, index) argmin keys of the rows [Ns] and the columns [Nt]
+struct NnKeys {
+    unsigned long long *rk, *ck;
+};
+static NnKeys bind_nn_keys(Carve &c, int Ns, int Nt) {
+    NnKeys k;
+    k.rk = c.take<unsigned long long>((size_t)Ns);
+    k.ck = c.take<unsigned long long>((size_t)Nt);
+    return k;
 }
 
+size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
+    Carve c(nullptr);
+    bind_nn_keys(c, Ns, Nt);
+    return c.off;
+}
 
 int32_t pdsc_mutual_nn(const float *src_desc, const float *tgt_desc, int32_t Ns, int32_t Nt, int32_t D,
                        int32_t *nn_src, int32_t *nn_tgt, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
@@ -1502,7 +1555,8 @@ int32_t pdsc_mutual_nn(const float *src_desc, const float *tgt_desc, int32_t Ns,
     if (!nn_src || !nn_tgt) return fail(PDSC_ERR_ARG, "null pointer");
     hipStream_t s = S_(stream);
     Carve c(ws);
-    unsigned long long *rk = c.take<unsigned long long>(Ns), *ck = c.take<unsigned long long>(Nt);
+    const NnKeys nk = bind_nn_keys(c, Ns, Nt);
+    unsigned long long *rk = nk.rk, *ck = nk.ck;
     HIPCHK(launch_nn_argmin(src_desc, tgt_desc, Ns, Nt, D, rk, ck, s));
     hipLaunchKernelGGL(unpack_nn_kernel, dim3((Ns + 255) / 256), dim3(256), 0, s, rk, Ns, nn_src);
     hipLaunchKernelGGL(unpack_nn_kernel, dim3((Nt + 255) / 256), dim3(256), 0, s, ck, Nt, nn_tgt);
@@ -1521,7 +1575,8 @@ int32_t pdsc_build_correspondences(const float *src_desc, const float *tgt_desc,
     if (gt_trans && !labels) return fail(PDSC_ERR_ARG, "gt_trans given without labels");
     hipStream_t s = S_(stream);
     Carve c(ws);
-    unsigned long long *rk = c.take<unsigned long long>(Ns), *ck = c.take<unsigned long long>(Nt);
+    const NnKeys nk = bind_nn_keys(c, Ns, Nt);
+    unsigned long long *rk = nk.rk, *ck = nk.ck;
     HIPCHK(launch_nn_argmin(src_desc, tgt_desc, Ns, Nt, D, rk, ck, s));
     HIPCHK(launch_corr_build(rk, ck, src_xyz, tgt_xyz, Ns, mutual ? 1 : 0, gt_trans, inlier_threshold, corr, count,
                              corr_pos, src_keypts, tgt_keypts, gt_trans ? labels : nullptr, s));
@@ -1529,8 +1584,22 @@ int32_t pdsc_build_correspondences(const float *src_desc, const float *tgt_desc,
 }
 
 // ------------------------------------------------ f3 spectral-matching baseline
+// M [N][N] and the power iteration's v, y, w [N]
+struct SmBufs {
+    float *M, *v, *y, *w;
+};
+static void bind_sm(Carve &c, int N, SmBufs &W) {
+    W.M = c.take<float>((size_t)N * N);
+    W.v = c.take<float>((size_t)N);
+    W.y = c.take<float>((size_t)N);
+    W.w = c.take<float>((size_t)N);
+}
+
 size_t pdsc_spectral_matching_workspace_bytes(int32_t N) {
-    return align_bytes((size_t)N * N * sizeof(float)) + 3 * align_bytes((size_t)N * sizeof(float));
+    Carve c(nullptr);
+    SmBufs W;
+    bind_sm(c, N, W);
+    return c.off;
 }
 
 int32_t pdsc_spectral_matching(const float *corr_pos, const float *src, const float *tgt, int32_t N,
@@ -1542,8 +1611,9 @@ int32_t pdsc_spectral_matching(const float *corr_pos, const float *src, const fl
                     inlier_threshold);
     RET_IF(need_ws(ws_bytes, pdsc_spectral_matching_workspace_bytes(N)));
     Carve c(ws);
-    float *M = c.take<float>((size_t)N * N), *v = c.take<float>(N), *y = c.take<float>(N), *w = c.take<float>(N);
-    if (leading_eig) v = leading_eig;
+    SmBufs W;
+    bind_sm(c, N, W);
+    float *M = W.M, *v = leading_eig ? leading_eig : W.v, *y = W.y, *w = W.w;
     const double sigma = inlier_threshold / 3.0;  // :34 (python float)
     const float sig2 = (float)(sigma * sigma);    // tensor / python scalar -> fp32 divisor
     const int S = (int)(N * top_ratio);           // int(leading_eig.shape[1] * top_ratio) (:46)

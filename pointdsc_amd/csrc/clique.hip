@@ -14,6 +14,7 @@
 // no integer atomics on global memory either: every output word has one writer,
 // so two calls are bitwise equal.  DESIGN.md §7 "PMC baseline" has the algorithm.
 #include "pdsc_internal.hpp"
+#include "workspace.hpp"
 
 #pragma clang fp contract(off)
 
@@ -548,10 +549,9 @@ struct CliqueWs {
     CliqueState *st;
     SearchOut out;
     int G, depth;
-    size_t bytes;
 };
 
-CliqueWs carve_clique(void *ws, int N) {
+CliqueWs carve_clique(Carve &k, int N) {
     const int W = (N + 63) / 64;
     CliqueWs c;
     c.depth = N < CLIQUE_DEPTH ? N : CLIQUE_DEPTH;
@@ -559,30 +559,22 @@ CliqueWs carve_clique(void *ws, int N) {
     size_t stack_bytes = (size_t)N * level;  // monotone in N; capped
     if (stack_bytes > STACK_BYTES_MAX) stack_bytes = STACK_BYTES_MAX;
     c.G = (int)(stack_bytes / level);  // >= 1: one level set is at most 256 KiB
-    char *base = static_cast<char *>(ws);
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char *p = base ? base + off : nullptr;
-        off += align_bytes(n);
-        return p;
-    };
-    c.st = reinterpret_cast<CliqueState *>(take(sizeof(CliqueState)));
-    c.deg0 = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.hsize = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.rdeg = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.order = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.alive[0] = reinterpret_cast<u64 *>(take((size_t)W * 8));
-    c.alive[1] = reinterpret_cast<u64 *>(take((size_t)W * 8));
-    c.best_orig = reinterpret_cast<u64 *>(take((size_t)W * 8));
-    c.adj2 = reinterpret_cast<u64 *>(take((size_t)N * W * 8));
+    c.st = k.take<CliqueState>(1);
+    c.deg0 = k.take<int>((size_t)N);
+    c.hsize = k.take<int>((size_t)N);
+    c.rdeg = k.take<int>((size_t)N);
+    c.order = k.take<int>((size_t)N);
+    c.alive[0] = k.take<u64>((size_t)W);
+    c.alive[1] = k.take<u64>((size_t)W);
+    c.best_orig = k.take<u64>((size_t)W);
+    c.adj2 = k.take<u64>((size_t)N * W);
     // the per-wave slots are sized for N waves (G <= N), so that the total is monotone in N
-    c.out.wsize = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.out.wroot = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.out.wincomp = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.out.wnodes = reinterpret_cast<long long *>(take((size_t)N * 8));
-    c.out.wbest = reinterpret_cast<u64 *>(take((size_t)N * W * 8));
-    c.stack = reinterpret_cast<u64 *>(take(stack_bytes));
-    c.bytes = off;
+    c.out.wsize = k.take<int>((size_t)N);
+    c.out.wroot = k.take<int>((size_t)N);
+    c.out.wincomp = k.take<int>((size_t)N);
+    c.out.wnodes = k.take<long long>((size_t)N);
+    c.out.wbest = k.take<u64>((size_t)N * W);
+    c.stack = reinterpret_cast<u64 *>(k.take_bytes(stack_bytes));
     return c;
 }
 
@@ -590,7 +582,8 @@ template <int WPL>
 hipError_t run_clique(const u64 *adj, int N, long long budget, bool exact, int *members, pdsc_clique_result *res,
                       float *labels, void *ws, hipStream_t s) {
     const int W = (N + 63) / 64;
-    const CliqueWs c = carve_clique(ws, N);
+    Carve k(ws);
+    const CliqueWs c = carve_clique(k, N);
     const int rows4 = (N + 3) / 4;
     hipLaunchKernelGGL(degree_kernel, dim3(rows4), dim3(256), 0, s, adj, N, W, c.deg0);
     hipLaunchKernelGGL(greedy_kernel<WPL>, dim3(rows4), dim3(256), 0, s, adj, c.deg0, N, W, c.hsize);
@@ -632,7 +625,17 @@ hipError_t launch_consistency_graph(const float *corr_pos, int N, double thr, bo
 }
 
 int clique_depth() { return CLIQUE_DEPTH; }
-size_t clique_workspace_bytes(int N) { return carve_clique(nullptr, N).bytes; }
+size_t clique_workspace_bytes(int N) {
+    Carve k(nullptr);
+    carve_clique(k, N);
+    return k.off;
+}
+
+void *reserve_clique(Carve &k, int N) {
+    void *ws = k.take_bytes(0);  // where the next slice starts
+    carve_clique(k, N);
+    return ws;
+}
 
 hipError_t launch_max_clique(const u64 *adj, int N, long long budget, bool exact, int *members, pdsc_clique_result *res,
                              float *labels, void *ws, hipStream_t s) {

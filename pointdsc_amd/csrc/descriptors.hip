@@ -36,6 +36,7 @@
 
 #include "pdsc_common.hpp"
 #include "pdsc_internal.hpp"
+#include "workspace.hpp"
 
 namespace pdsc {
 
@@ -538,51 +539,50 @@ __global__ __launch_bounds__(256) void fpfh_kernel(int n, const int *__restrict_
 }
 
 // ------------------------------------------------------------------ launchers
-size_t grid_workspace_bytes(int n) {
-    size_t a = 0, b = 0, c = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const u64 *)nullptr, (u64 *)nullptr, (const int *)nullptr,
-                                             (int *)nullptr, n, 0, 3 * KEY_BITS);
-    (void)hipcub::DeviceRunLengthEncode::Encode(nullptr, b, (const u64 *)nullptr, (u64 *)nullptr, (int *)nullptr,
+// the temp bytes hipcub asks for: [0] the radix sort, [1] the run-length encode, [2] the scan; returns the largest
+static size_t grid_cub_bytes(int n, size_t bytes[3]) {
+    bytes[0] = bytes[1] = bytes[2] = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, bytes[0], (const u64 *)nullptr, (u64 *)nullptr,
+                                             (const int *)nullptr, (int *)nullptr, n, 0, 3 * KEY_BITS);
+    (void)hipcub::DeviceRunLengthEncode::Encode(nullptr, bytes[1], (const u64 *)nullptr, (u64 *)nullptr, (int *)nullptr,
                                                 (int *)nullptr, n);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, c, (const int *)nullptr, (int *)nullptr, n);
-    const size_t cub = std::max(a, std::max(b, c));
-    const size_t nn = (size_t)std::max(n, 1);
-    return align_bytes(ST_BLOCKS * 3 * (2 * sizeof(float) + sizeof(double))) + align_bytes(sizeof(CloudStats)) +
-           3 * align_bytes(nn * sizeof(u64)) + 5 * align_bytes(nn * sizeof(int)) + align_bytes(4 * sizeof(int)) +
-           align_bytes(cub);
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes[2], (const int *)nullptr, (int *)nullptr, n);
+    return std::max(bytes[0], std::max(bytes[1], bytes[2]));
 }
 
-hipError_t build_grid(const float *pts, int n, double cell, double half, void *ws, GridBufs &G, hipStream_t s) {
-    char *w = static_cast<char *>(ws);
-    auto take = [&](size_t bytes) {
-        char *p = w;
-        w += align_bytes(bytes);
-        return p;
-    };
+void bind_grid(Carve &c, int n, GridBufs &G) {
     const size_t nn = (size_t)std::max(n, 1);
-    float *pmn = reinterpret_cast<float *>(take(ST_BLOCKS * 3 * (2 * sizeof(float) + sizeof(double))));
-    float *pmx = pmn + ST_BLOCKS * 3;
+    G.stats = c.take_bytes(ST_BLOCKS * 3 * (2 * sizeof(float) + sizeof(double)));  // min, max (float), sum (double)
+    G.st = c.take<CloudStats>(1);
+    G.key = c.take<u64>(nn);
+    G.view.skey = c.take<u64>(nn);
+    G.view.ukey = c.take<u64>(nn);
+    G.idx = c.take<int>(nn);
+    G.view.sidx = c.take<int>(nn);
+    G.view.ustart = c.take<int>(nn);
+    G.view.ucount = c.take<int>(nn);
+    c.take<int>(nn);  // reserved
+    G.flags = c.take<int>(4);
+    G.view.nruns = G.flags;
+    G.err = G.flags ? G.flags + 1 : nullptr;  // [0] range, [1] kNN capacity
+    G.cub = c.take_bytes(grid_cub_bytes(n, G.cub_bytes));
+}
+
+size_t grid_workspace_bytes(int n) {
+    Carve c(nullptr);
+    GridBufs G;
+    bind_grid(c, n, G);
+    return c.off;
+}
+
+hipError_t build_grid(const float *pts, int n, double cell, double half, const GridBufs &G, hipStream_t s) {
+    const size_t nn = (size_t)std::max(n, 1);
+    float *pmn = reinterpret_cast<float *>(G.stats), *pmx = pmn + ST_BLOCKS * 3;
     double *psum = reinterpret_cast<double *>(pmx + ST_BLOCKS * 3);
-    G.st = reinterpret_cast<CloudStats *>(take(sizeof(CloudStats)));
-    u64 *key = reinterpret_cast<u64 *>(take(nn * sizeof(u64)));
-    G.view.skey = reinterpret_cast<u64 *>(take(nn * sizeof(u64)));
-    G.view.ukey = reinterpret_cast<u64 *>(take(nn * sizeof(u64)));
-    int *idx = reinterpret_cast<int *>(take(nn * sizeof(int)));
-    G.view.sidx = reinterpret_cast<int *>(take(nn * sizeof(int)));
-    G.view.ustart = reinterpret_cast<int *>(take(nn * sizeof(int)));
-    G.view.ucount = reinterpret_cast<int *>(take(nn * sizeof(int)));
-    take(nn * sizeof(int));  // reserved
-    int *flags = reinterpret_cast<int *>(take(4 * sizeof(int)));
-    G.view.nruns = flags;
-    G.err = flags + 1;  // [0] range, [1] kNN capacity
-    size_t cub = 0, a = 0, b = 0, c = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const u64 *)nullptr, (u64 *)nullptr, (const int *)nullptr,
-                                             (int *)nullptr, n, 0, 3 * KEY_BITS);
-    (void)hipcub::DeviceRunLengthEncode::Encode(nullptr, b, (const u64 *)nullptr, (u64 *)nullptr, (int *)nullptr,
-                                                (int *)nullptr, n);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, c, (const int *)nullptr, (int *)nullptr, n);
-    cub = std::max(a, std::max(b, c));
-    void *tmp = take(cub);
+    u64 *key = G.key;
+    int *idx = G.idx, *flags = G.flags;
+    void *tmp = G.cub;
+    const size_t a = G.cub_bytes[0], b = G.cub_bytes[1], c = G.cub_bytes[2];
     hipError_t e;
     if ((e = hipMemsetAsync(flags, 0, 4 * sizeof(int), s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(G.view.ucount, 0, nn * sizeof(int), s)) != hipSuccess) return e;

@@ -237,12 +237,7 @@ __global__ __launch_bounds__(GC_LABEL_WG) void gc_label_kernel(GcLabelArgs A) {
     const int cell0 = blockIdx.x * GC_CELLS_PER_WG;
     if (cell0 >= ncell) return;
     double c[12];
-    {
-        const double *T = A.pose;
-        c[0] = T[0], c[1] = T[1], c[2] = T[2], c[9] = T[3];
-        c[3] = T[4], c[4] = T[5], c[5] = T[6], c[10] = T[7];
-        c[6] = T[8], c[7] = T[9], c[8] = T[10], c[11] = T[11];
-    }
+    pose12(A.pose, c);
     const double inf = INFINITY;
     // cells of up to 64 rows: a wave each, a row per lane
     if (cell0 + w < ncell) {
@@ -327,19 +322,12 @@ struct GcState {
     int rvalid, lo_active, iterations, lo_runs, lo_steps, n_lab;
 };
 
-PDSC_DEV void gc_pose16(const double c[12], double T[16]) {
-    T[0] = c[0], T[1] = c[1], T[2] = c[2], T[3] = c[9];
-    T[4] = c[3], T[5] = c[4], T[6] = c[5], T[7] = c[10];
-    T[8] = c[6], T[9] = c[7], T[10] = c[8], T[11] = c[11];
-    T[12] = 0.0, T[13] = 0.0, T[14] = 0.0, T[15] = 1.0;
-}
-
 __global__ __launch_bounds__(256) void gc_init_kernel(GcState *st, RansacState *rs, int H, int *dbg_count) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (dbg_count && i < (size_t)H) dbg_count[i] = -3;
+    debug_prefill(dbg_count, H, i);
     if (i == 0) {
         for (int k = 0; k < 12; ++k) st->c[k] = st->rc[k] = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
-        gc_pose16(st->c, st->T);
+        pose16(st->c, st->T);
         st->score = st->rscore = -1.0;
         st->count = st->rcount = -1;
         st->best = st->rbest = -1;
@@ -348,53 +336,27 @@ __global__ __launch_bounds__(256) void gc_init_kernel(GcState *st, RansacState *
     }
 }
 
-struct GcCand {
-    double sc;
-    int cnt, h, slot;
+// (score desc, h asc): a total order over distinct h, so the shape of
+// round_best's reduction tree cannot change the winner
+struct GcBetter {
+    PDSC_DEV bool operator()(const Cand &a, const Cand &b) const { return a.s > b.s || (a.s == b.s && a.h < b.h); }
 };
-// (score desc, h asc): a total order over distinct h
-PDSC_DEV bool gc_better(const GcCand &a, const GcCand &b) { return a.sc > b.sc || (a.sc == b.sc && a.h < b.h); }
 
 __global__ __launch_bounds__(RANSAC_FIN) void gc_round_kernel(int nwg, int nchunks, int round, int H, int lo,
                                                               RansacBufs B, GcState *st, pdsc_ransac_debug dbg) {
-    __shared__ GcCand wbest[RANSAC_FIN / 64];
+    __shared__ Cand wbest[RANSAC_FIN / 64];
     if (B.st->done) return;  // workgroup-uniform
     const int tid = threadIdx.x;
-    int total = 0;
-    for (int k = 0; k < nwg; ++k) total += B.wgcount[k];
-    GcCand best = {-1.0, -1, 0x7fffffff, 0};
-    for (int g = tid; g < total; g += RANSAC_FIN) {
-        GcCand x = {0.0, 0, 0, B.gslot[g]};
-        for (int ch = 0; ch < nchunks; ++ch) {  // chunk order
-            x.cnt += B.pcount[(size_t)ch * RANSAC_ROUND + g];
-            x.sc += B.psum[(size_t)ch * RANSAC_ROUND + g];
-        }
-        x.h = B.hidx[x.slot];
-        if (dbg.count) dbg.count[x.h] = x.cnt;
-        if (dbg.sumsq) dbg.sumsq[x.h] = x.sc;
-        if (gc_better(x, best)) best = x;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        GcCand y;
-        y.sc = __shfl_xor(best.sc, o);
-        y.cnt = __shfl_xor(best.cnt, o);
-        y.h = __shfl_xor(best.h, o);
-        y.slot = __shfl_xor(best.slot, o);
-        if (gc_better(y, best)) best = y;
-    }
-    if ((tid & 63) == 0) wbest[tid >> 6] = best;
-    __syncthreads();
+    int total;
+    const Cand best = round_best(B, nwg, nchunks, dbg, Cand{-1.0, -1, 0x7fffffff, 0}, wbest, tid, total, GcBetter{});
     if (tid != 0) return;
-    for (int k = 1; k < RANSAC_FIN / 64; ++k)
-        if (gc_better(wbest[k], best)) best = wbest[k];
     st->rvalid = 0;
     st->lo_active = 0;
     st->n_lab = 0;
-    if (best.cnt >= 0 && best.sc > st->score) {
+    if (best.cnt >= 0 && best.s > st->score) {
         for (int k = 0; k < 12; ++k) st->rc[k] = B.coef[(size_t)k * RANSAC_ROUND + best.slot];
-        gc_pose16(st->rc, st->T);
-        st->rscore = best.sc;
+        pose16(st->rc, st->T);
+        st->rscore = best.s;
         st->rcount = best.cnt;
         st->rbest = best.h;
         st->rvalid = 1;
@@ -461,7 +423,7 @@ __global__ __launch_bounds__(RANSAC_FIN) void gc_lo_kernel(const float *__restri
     for (int ch = 0; ch < nchunks; ++ch) cnt += ccnt[ch], sc += csum[ch];
     if (sc > st->rscore) {
         for (int k = 0; k < 12; ++k) st->rc[k] = c[k];
-        gc_pose16(c, st->T);
+        pose16(c, st->T);
         st->rscore = sc;
         st->rcount = cnt;
     } else {
@@ -480,15 +442,7 @@ __global__ void gc_fold_kernel(int N, int round, double confidence, RansacState 
     }
     st->rvalid = 0;
     st->lo_active = 0;
-    if (confidence < 1.0 && st->count > 0) {
-        bool stop = st->count == N;  // f = 1: the criterion's log(0)
-        if (!stop) {
-            const double drawn = (double)(((long long)round + 1) * RANSAC_ROUND);
-            const double f = (double)st->count / (double)N;
-            stop = drawn >= log(1.0 - confidence) / log(1.0 - f * f * f);
-        }
-        if (stop) rs->done = 1;
-    }
+    if (confidence_stop(st->count, N, 3, ((long long)round + 1) * RANSAC_ROUND, confidence)) rs->done = 1;
 }
 
 // labels and count of the so-far-best under d^2 < r2, then pdsc_refit_inliers' fit over them
@@ -504,21 +458,12 @@ __global__ __launch_bounds__(RANSAC_FIN) void gc_finish_kernel(const float *__re
 #pragma unroll
     for (int k = 0; k < 12; ++k) c[k] = st->c[k];
     double n = 0.0, sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0};
-    for (int i = tid; i < N; i += RANSAC_FIN) {
-        const D3 a = load3(src, i), b = load3(tgt, i);
-        const bool in = count >= 0 && ransac_d2(c, a.x, a.y, a.z, b.x, b.y, b.z) < r2;
-        if (labels) labels[i] = in ? 1.0f : 0.0f;
-        if (in) {
-            n += 1.0;
-            sa[0] += a.x, sa[1] += a.y, sa[2] += a.z;
-            sb[0] += b.x, sb[1] += b.y, sb[2] += b.z;
-        }
-    }
+    label_inliers(src, tgt, N, c, r2, count >= 0, labels, n, sa, sb, tid);
     n = block_sum(n, red, tid);  // workgroup-uniform
     if (n >= 3.0) refit_kabsch(src, tgt, N, r2, n, sa, sb, c, red, tid);
     if (tid != 0) return;
     double T[16];
-    gc_pose16(c, T);
+    pose16(c, T);
     if (res) {
         for (int i = 0; i < 16; ++i) res->trans[i] = T[i];
         res->score = count >= 0 ? st->score : 0.0;
@@ -534,26 +479,40 @@ __global__ __launch_bounds__(RANSAC_FIN) void gc_finish_kernel(const float *__re
 }
 
 // ------------------------------------------------------------------- launchers
-size_t gc_grid_workspace_bytes(int N) { return align_bytes((size_t)N * sizeof(u64)); }
+// the grid kernel's scratch: the keys of the in-global-memory sort
+static u64 *bind_gc_grid(Carve &c, int N) { return c.take<u64>((size_t)N); }
 
-hipError_t launch_gc_grid(const float *src, const float *tgt, int N, int G, int *order, int *cell_start, int *cell_of,
-                          int *n_cells, void *ws, hipStream_t s) {
-    hipLaunchKernelGGL(gc_grid_kernel, dim3(1), dim3(GC_GRID_WG), 0, s, src, tgt, N, G, static_cast<u64 *>(ws), order,
-                       cell_start, cell_of, n_cells);
+size_t gc_grid_workspace_bytes(int N) {
+    Carve c(nullptr);
+    bind_gc_grid(c, N);
+    return c.off;
+}
+
+static hipError_t gc_grid_enqueue(const float *src, const float *tgt, int N, int G, u64 *gkey, int *order,
+                                  int *cell_start, int *cell_of, int *n_cells, hipStream_t s) {
+    hipLaunchKernelGGL(gc_grid_kernel, dim3(1), dim3(GC_GRID_WG), 0, s, src, tgt, N, G, gkey, order, cell_start,
+                       cell_of, n_cells);
     return hipGetLastError();
 }
 
-size_t gc_label_workspace_bytes(int N) {
-    return align_bytes((size_t)N * sizeof(u64)) + align_bytes((size_t)N * sizeof(int)) +
-           align_bytes((size_t)N * sizeof(double));
+hipError_t launch_gc_grid(const float *src, const float *tgt, int N, int G, int *order, int *cell_start, int *cell_of,
+                          int *n_cells, void *ws, hipStream_t s) {
+    Carve c(ws);
+    return gc_grid_enqueue(src, tgt, N, G, bind_gc_grid(c, N), order, cell_start, cell_of, n_cells, s);
 }
 
-static void gc_label_bind(char *w, int N, GcLabelArgs &A) {
-    A.skey = reinterpret_cast<u64 *>(w);
-    w += align_bytes((size_t)N * sizeof(u64));
-    A.srow = reinterpret_cast<int *>(w);
-    w += align_bytes((size_t)N * sizeof(int));
-    A.sP = reinterpret_cast<double *>(w);
+// the label kernel's scratch for cells above GC_LDS_CELL rows
+static void bind_gc_label(Carve &c, int N, GcLabelArgs &A) {
+    A.skey = c.take<u64>((size_t)N);
+    A.srow = c.take<int>((size_t)N);
+    A.sP = c.take<double>((size_t)N);
+}
+
+size_t gc_label_workspace_bytes(int N) {
+    Carve c(nullptr);
+    GcLabelArgs A;
+    bind_gc_label(c, N, A);
+    return c.off;
 }
 
 static hipError_t gc_label_enqueue(const GcLabelArgs &A, int N, hipStream_t s) {
@@ -571,70 +530,78 @@ hipError_t launch_gc_label(const double *pose, const float *src, const float *tg
     A.dbg = pdsc_gc_label_debug{nullptr, nullptr, nullptr, nullptr};
     if (debug) A.dbg = *debug;
     A.gate = nullptr, A.done = nullptr;
-    gc_label_bind(static_cast<char *>(ws), N, A);
+    Carve c(ws);
+    bind_gc_label(c, N, A);
     HIP_RET(hipMemsetAsync(count, 0, sizeof(int), s));
     return gc_label_enqueue(A, N, s);
 }
 
+// The solver's workspace: the round buffers, its state, the grid (scratch and outputs) and the LO's labelling.
+struct GcBufs {
+    RansacBufs B;
+    GcState *st;
+    u64 *gkey;
+    int *order, *cell_of, *cell_start, *n_cells;
+    GcLabelArgs A;  // its three scratch arrays
+    float *lab;
+};
+static void bind_gc_ransac(Carve &c, int N, GcBufs &W) {
+    bind_ransac(c, N, W.B);
+    W.st = c.take<GcState>(1);
+    W.gkey = bind_gc_grid(c, N);
+    W.order = c.take<int>((size_t)N);
+    W.cell_of = c.take<int>((size_t)N);
+    W.cell_start = c.take<int>((size_t)N + 1);
+    W.n_cells = c.take<int>(1);
+    bind_gc_label(c, N, W.A);
+    W.lab = c.take<float>((size_t)N);
+}
+
 size_t gc_ransac_workspace_bytes(int N) {
-    return ransac_workspace_bytes(N) + align_bytes(sizeof(GcState)) + gc_grid_workspace_bytes(N) +
-           2 * align_bytes((size_t)N * sizeof(int)) + align_bytes(((size_t)N + 1) * sizeof(int)) +
-           align_bytes(sizeof(int)) + gc_label_workspace_bytes(N) + align_bytes((size_t)N * sizeof(float));
+    Carve c(nullptr);
+    GcBufs W;
+    bind_gc_ransac(c, N, W);
+    return c.off;
 }
 
 hipError_t launch_gc_ransac(const float *src, const float *tgt, int N, double threshold, double lambda, int G, int H,
                             double confidence, unsigned long long seed, int lo, float *trans_f32, float *labels,
                             pdsc_gc_ransac_result *res, const pdsc_gc_ransac_debug *debug, void *ws, hipStream_t s) {
-    const size_t R = RANSAC_ROUND;
     const int nchunks = (int)ransac_chunks(N);
-    RansacBufs B;
-    char *w = ransac_bind(static_cast<char *>(ws), N, B);
-    auto take = [&w](size_t bytes) {
-        char *p = w;
-        w += align_bytes(bytes);
-        return p;
-    };
-    GcState *st = reinterpret_cast<GcState *>(take(sizeof(GcState)));
-    void *grid_ws = take(gc_grid_workspace_bytes(N));
-    int *order = reinterpret_cast<int *>(take((size_t)N * sizeof(int)));
-    int *cell_of = reinterpret_cast<int *>(take((size_t)N * sizeof(int)));
-    int *cell_start = reinterpret_cast<int *>(take(((size_t)N + 1) * sizeof(int)));
-    int *n_cells = reinterpret_cast<int *>(take(sizeof(int)));
-    char *label_ws = take(gc_label_workspace_bytes(N));
-    float *lab = reinterpret_cast<float *>(take((size_t)N * sizeof(float)));
+    Carve c(ws);
+    GcBufs W;
+    bind_gc_ransac(c, N, W);
+    const RansacBufs &B = W.B;
+    GcState *st = W.st;
+    GcLabelArgs &A = W.A;
     pdsc_ransac_debug dbg = {nullptr, nullptr, nullptr, nullptr};
     if (debug) dbg = pdsc_ransac_debug{debug->samples, debug->count, debug->score, debug->trans};
     const double r2 = threshold * threshold;
     const int init_blocks = dbg.count ? (int)(((size_t)H + 255) / 256) : 1;
     hipLaunchKernelGGL(gc_init_kernel, dim3(init_blocks), dim3(256), 0, s, st, B.st, H, dbg.count);
-    GcLabelArgs A;
     if (lo) {
-        HIP_RET(launch_gc_grid(src, tgt, N, G, order, cell_start, cell_of, n_cells, grid_ws, s));
-        A.pose = st->T, A.src = src, A.tgt = tgt, A.order = order, A.cell_start = cell_start, A.n_cells = n_cells;
+        HIP_RET(gc_grid_enqueue(src, tgt, N, G, W.gkey, W.order, W.cell_start, W.cell_of, W.n_cells, s));
+        A.pose = st->T, A.src = src, A.tgt = tgt, A.order = W.order, A.cell_start = W.cell_start, A.n_cells = W.n_cells;
         A.den = 2.0 * r2, A.lambda = lambda;
-        A.labels = lab, A.count = &st->n_lab;
+        A.labels = W.lab, A.count = &st->n_lab;
         A.dbg = pdsc_gc_label_debug{nullptr, nullptr, nullptr, nullptr};
         A.gate = &st->lo_active, A.done = &B.st->done;
-        gc_label_bind(label_ws, N, A);
     }
-    const int rounds = (int)(((size_t)H + R - 1) / R);
-    for (int r = 0; r < rounds; ++r) {
-        const long long base = (long long)r * RANSAC_ROUND;
-        const int nh = (int)((long long)H - base < (long long)R ? (long long)H - base : (long long)R);
-        const int nwg = (nh + RANSAC_HWG - 1) / RANSAC_HWG;
-        hipLaunchKernelGGL(ransac_hyp_kernel<3>, dim3(nwg), dim3(RANSAC_HWG), 0, s, src, tgt, N, (int)base, H, (u64)seed,
+    for (int r = 0, rounds = ransac_rounds(H); r < rounds; ++r) {
+        const RoundShape q = ransac_round_shape(H, r);
+        hipLaunchKernelGGL(ransac_hyp_kernel<3>, dim3(q.nwg), dim3(RANSAC_HWG), 0, s, src, tgt, N, q.base, H, (u64)seed,
                            0.0, B, dbg);
-        hipLaunchKernelGGL(ransac_score_kernel<true>, dim3((nh + 63) / 64, nchunks), dim3(64), 0, s, src, tgt, N, nwg,
-                           r2, B);
-        hipLaunchKernelGGL(gc_round_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, nwg, nchunks, r, H, lo, B, st, dbg);
+        hipLaunchKernelGGL(ransac_score_kernel<true>, dim3((q.nh + 63) / 64, nchunks), dim3(64), 0, s, src, tgt, N,
+                           q.nwg, r2, B);
+        hipLaunchKernelGGL(gc_round_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, q.nwg, nchunks, r, H, lo, B, st, dbg);
         for (int step = 0; lo && step < GC_LO_STEPS; ++step) {
             HIP_RET(gc_label_enqueue(A, N, s));
-            hipLaunchKernelGGL(gc_lo_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, src, tgt, N, r2, lab, B.st, st);
+            hipLaunchKernelGGL(gc_lo_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, src, tgt, N, r2, W.lab, B.st, st);
         }
         hipLaunchKernelGGL(gc_fold_kernel, dim3(1), dim3(64), 0, s, N, r, confidence, B.st, st);
         HIP_RET(hipGetLastError());
     }
-    hipLaunchKernelGGL(gc_finish_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, src, tgt, N, r2, st, lo ? n_cells : nullptr,
+    hipLaunchKernelGGL(gc_finish_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, src, tgt, N, r2, st, lo ? W.n_cells : nullptr,
                        trans_f32, labels, res);
     return hipGetLastError();
 }

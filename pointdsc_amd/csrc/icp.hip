@@ -28,6 +28,7 @@
 // functions between __syncthreads, so the results are bitwise the same).
 #include "pdsc_common.hpp"
 #include "pdsc_internal.hpp"
+#include "workspace.hpp"
 
 namespace pdsc {
 
@@ -278,18 +279,35 @@ __global__ __launch_bounds__(ICP_WG) void icp_one_wg_kernel(const float *__restr
 // ------------------------------------------------------------------ launchers
 static size_t icp_chunks(int Ns) { return ((size_t)Ns + ICP_CHUNK - 1) / ICP_CHUNK; }
 
+// the target's grid, the state block and the partial rows [nchunks][ICP_NSUM]
+struct IcpBufs {
+    GridBufs grid;
+    IcpState *st;
+    double *part;
+};
+static void bind_icp(Carve &c, int Ns, int Nt, IcpBufs &I) {
+    bind_grid(c, Nt, I.grid);
+    I.st = c.take<IcpState>(1);
+    I.part = c.take<double>(icp_chunks(Ns) * ICP_NSUM);
+}
+
 size_t icp_workspace_bytes(int Ns, int Nt) {
-    return grid_workspace_bytes(Nt) + align_bytes(sizeof(IcpState)) +
-           align_bytes(icp_chunks(Ns) * ICP_NSUM * sizeof(double));
+    Carve c(nullptr);
+    IcpBufs I;
+    bind_icp(c, Ns, Nt, I);
+    return c.off;
 }
 
 hipError_t launch_icp(const float *src, int Ns, const float *tgt, int Nt, const double *init, double max_distance,
                       int max_iter, double rel_fitness, double rel_rmse, bool one_wg, float *trans_f32,
                       pdsc_icp_result *res, int *corr, void *ws, GridBufs &G, hipStream_t s) {
-    HIP_RET(build_grid(tgt, Nt, max_distance, 0.0, ws, G, s));
-    char *w = static_cast<char *>(ws) + grid_workspace_bytes(Nt);
-    IcpState *st = reinterpret_cast<IcpState *>(w);
-    double *part = reinterpret_cast<double *>(w + align_bytes(sizeof(IcpState)));
+    Carve c(ws);
+    IcpBufs I;
+    bind_icp(c, Ns, Nt, I);
+    G = I.grid;
+    HIP_RET(build_grid(tgt, Nt, max_distance, 0.0, G, s));
+    IcpState *st = I.st;
+    double *part = I.part;
     const double r2 = max_distance * max_distance;
     const int nchunks = (int)icp_chunks(Ns);
     if (one_wg && Ns <= ICP_ONE_WG_MAX) {

@@ -28,6 +28,7 @@
 //
 // Integer atomics only: two calls are bitwise equal.
 #include "pdsc_internal.hpp"
+#include "workspace.hpp"
 
 namespace pdsc {
 
@@ -165,8 +166,20 @@ int nn2_default_split(int Na, int Nb) {
     return s < 1 ? 1 : s;
 }
 
+struct Nn2Bufs {
+    u64 *rowpart;  // [NN2_MAX_SPLIT][Na][2] the splits' two best keys per row
+    u64 *colkey;   // [Nb] the best key per column
+};
+static void bind_nn2(Carve &c, int Na, int Nb, Nn2Bufs &W) {
+    W.rowpart = c.take<u64>((size_t)NN2_MAX_SPLIT * Na * 2);
+    W.colkey = c.take<u64>((size_t)Nb);
+}
+
 size_t nn2_workspace_bytes(int Na, int Nb) {
-    return align_bytes((size_t)NN2_MAX_SPLIT * Na * 2 * sizeof(u64)) + align_bytes((size_t)Nb * sizeof(u64));
+    Carve c(nullptr);
+    Nn2Bufs W;
+    bind_nn2(c, Na, Nb, W);
+    return c.off;
 }
 
 hipError_t launch_nn2(const float *A, const float *B, int Na, int Nb, int D, int split, int *nn1, int *nn2, int *rev,
@@ -176,8 +189,10 @@ hipError_t launch_nn2(const float *A, const float *B, int Na, int Nb, int D, int
     int nsplit = split > 0 ? split : nn2_default_split(Na, Nb);
     if (nsplit > NN2_MAX_SPLIT) nsplit = NN2_MAX_SPLIT;
     if (nsplit > ntile) nsplit = ntile;
-    u64 *rowpart = static_cast<u64 *>(ws);
-    u64 *colkey = reinterpret_cast<u64 *>(static_cast<char *>(ws) + align_bytes((size_t)NN2_MAX_SPLIT * Na * 2 * sizeof(u64)));
+    Carve c(ws);
+    Nn2Bufs W;
+    bind_nn2(c, Na, Nb, W);
+    u64 *rowpart = W.rowpart, *colkey = W.colkey;
     HIP_RET(hipMemsetAsync(colkey, 0xff, (size_t)Nb * sizeof(u64), s));
     hipLaunchKernelGGL(nn2_kernel, dim3(nsplit, (Na + N2_T - 1) / N2_T), dim3(256), 0, s, A, B, Na, Nb, D, nsplit,
                        rowpart, colkey);
@@ -418,30 +433,30 @@ __global__ __launch_bounds__(1024) void gpf_compact_kernel(const int *__restrict
     if (tid == 0) count[0] = running;
 }
 
-size_t gpf_workspace_bytes(int N0, int G) {
+static void bind_gpf(Carve &c, int N0, int G, GpfBufs &B) {
     const size_t G2 = (size_t)G * G;
-    return 2 * align_bytes((size_t)N0 * sizeof(int)) + 4 * align_bytes(G2 * sizeof(int)) +
-           align_bytes((size_t)N0 * sizeof(u64));
+    B.cell = c.take<int>((size_t)N0);
+    B.keep = c.take<int>((size_t)N0);
+    B.cnt = c.take<int>(G2);
+    B.start = c.take<int>(G2);
+    B.cursor = c.take<int>(G2);
+    B.quota = c.take<int>(G2);
+    B.list = c.take<u64>((size_t)N0);
+}
+
+size_t gpf_workspace_bytes(int N0, int G) {
+    Carve c(nullptr);
+    GpfBufs B;
+    bind_gpf(c, N0, G, B);
+    return c.off;
 }
 
 hipError_t launch_gpf_select(const float *xyz0, const float *norm, const int *num_bb, int N0, int G, double factor,
                              int *kept, int *count, float *kept_norm, const pdsc_gpf_debug *debug, void *ws,
                              hipStream_t s) {
-    const size_t G2 = (size_t)G * G;
-    char *w = static_cast<char *>(ws);
-    auto take = [&w](size_t bytes) {
-        char *p = w;
-        w += align_bytes(bytes);
-        return p;
-    };
+    Carve c(ws);
     GpfBufs B;
-    B.cell = reinterpret_cast<int *>(take((size_t)N0 * sizeof(int)));
-    B.keep = reinterpret_cast<int *>(take((size_t)N0 * sizeof(int)));
-    B.cnt = reinterpret_cast<int *>(take(G2 * sizeof(int)));
-    B.start = reinterpret_cast<int *>(take(G2 * sizeof(int)));
-    B.cursor = reinterpret_cast<int *>(take(G2 * sizeof(int)));
-    B.quota = reinterpret_cast<int *>(take(G2 * sizeof(int)));
-    B.list = reinterpret_cast<u64 *>(take((size_t)N0 * sizeof(u64)));
+    bind_gpf(c, N0, G, B);
     pdsc_gpf_debug dbg = {nullptr, nullptr, nullptr, nullptr};
     if (debug) dbg = *debug;
     hipLaunchKernelGGL(gpf_cells_kernel, dim3(1), dim3(1024), 0, s, xyz0, N0, G, num_bb, factor, B, dbg);

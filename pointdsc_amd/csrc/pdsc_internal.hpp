@@ -16,6 +16,16 @@ constexpr int PT = 64;        // points per pointwise workgroup
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// a launcher's early return on a HIP error
+#define HIP_RET(expr)                      \
+    do {                                      \
+        hipError_t e_ = (expr);               \
+        if (e_ != hipSuccess) return e_;      \
+    } while (0)
+
+// workspace.hpp: the bump allocator every stage's layout function takes
+struct Carve;
+
 // ---- symmetric-packed M (the forward's a1 output) -------------------------
 // M is symmetric bit-for-bit, so the forward stores only its upper-triangle
 // MPACK_T x MPACK_T tiles, each contiguous and row-major, enumerated row by
@@ -28,7 +38,6 @@ __host__ __device__ inline size_t mpack_floats(int N) {
     return nt * (nt + 1) / 2 * MPACK_T * MPACK_T;
 }
 __host__ __device__ inline int mpack_tile(int ti, int tj, int nt) { return ti * nt - ti * (ti - 1) / 2 + (tj - ti); }
-inline size_t align_bytes(size_t x) { return (x + 255) & ~size_t(255); }
 
 // fp16 planes per packed 1x1-conv weight (3xfp16 mode): 2 = hi + mid (22
 // significant bits, products wh.xh + wh.xl + wm.xh: 3 MFMAs, as the attention's);
@@ -306,9 +315,17 @@ struct GridBufs {
     CloudStats *st;
     GridView view;
     int *err;  // [0] extent / cell >= 2^21, [1] a kNN candidate set over capacity
+    // build_grid's own scratch: the statistics partials, the unsorted keys and rows, the hipcub temp
+    char *stats;
+    unsigned long long *key;
+    int *idx, *flags;
+    void *cub;
+    size_t cub_bytes[3];  // of the radix sort, the run-length encode and the scan
 };
+// the grid's layout over n points: its size is what the carver has advanced by
+void bind_grid(Carve &c, int n, GridBufs &G);
 size_t grid_workspace_bytes(int n);
-hipError_t build_grid(const float *pts, int n, double cell, double half, void *ws, GridBufs &G, hipStream_t s);
+hipError_t build_grid(const float *pts, int n, double cell, double half, const GridBufs &G, hipStream_t s);
 hipError_t launch_radius_knn(const float *pts, int n, const GridBufs &G, double radius, int K, int *nbr, double *d2,
                              int *cnt, hipStream_t s);
 hipError_t launch_normals(const float *pts, int n, const int *nbr, const int *cnt, int K, const GridBufs &G,
@@ -385,6 +402,8 @@ hipError_t launch_consistency_graph(const float *corr_pos, int N, double thr, bo
                                     int *degree, hipStream_t s);
 int clique_depth();
 size_t clique_workspace_bytes(int N);
+// the same layout inside a caller's carver (teaser.hip); returns the base launch_max_clique takes as ws
+void *reserve_clique(Carve &c, int N);
 // exact = false: the greedy lower bound alone
 hipError_t launch_max_clique(const unsigned long long *adj, int N, long long budget, bool exact, int *members,
                              pdsc_clique_result *res, float *labels, void *ws, hipStream_t s);
@@ -404,11 +423,6 @@ hipError_t launch_teaser_solve(const float *src, const float *tgt, int N, double
                                float *trans_f32, float *labels, void *ws, hipStream_t s);
 
 // correspondence construction (corr.hip)
-#define HIP_RET(expr)                      \
-    do {                                      \
-        hipError_t e_ = (expr);               \
-        if (e_ != hipSuccess) return e_;      \
-    } while (0)
 // spectral-matching baseline (sm.hip)
 hipError_t launch_sm(const float *corr, const float *src, const float *tgt, int N, float sig2, int S, int iters,
                      float *M, float *v, float *y, float *w, float *labels, float *trans, hipStream_t s);

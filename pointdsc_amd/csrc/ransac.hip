@@ -23,8 +23,8 @@
 //   round        one workgroup adds each hypothesis's chunk rows in chunk
 //                order, reduces the round under (count desc, sumsq asc, h asc)
 //                -- a total order, so the reduction tree cannot change the
-//                winner -- folds it into the state block and applies the stop
-//                rule.
+//                winner (ransac_shared.hpp: round_best) -- folds it into the
+//                state block and applies the stop rule.
 //   finish       labels, the optional refit (fp64 Kabsch over the winner's
 //                inliers, centred, fixed order) and the result.
 //
@@ -36,11 +36,10 @@
 namespace pdsc {
 
 // ------------------------------------------------------------------------ init
-// The state block, and the debug rows' "never drawn" status (the rounds after an
-// early stop return at entry and cannot write it).
+// The state block and the debug rows' "never drawn" status.
 __global__ __launch_bounds__(256) void ransac_init_kernel(RansacState *st, int H, int *dbg_count) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (dbg_count && i < (size_t)H) dbg_count[i] = -3;
+    debug_prefill(dbg_count, H, i);
     if (i == 0) {
         for (int k = 0; k < 12; ++k) st->c[k] = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
         st->sumsq = 0.0;
@@ -54,69 +53,35 @@ __global__ __launch_bounds__(256) void ransac_init_kernel(RansacState *st, int H
 }
 
 // ----------------------------------------------------------------------- round
-struct RansacCand {
-    double ss;
-    int cnt, h, slot;
+// (count desc, sumsq asc, h asc): a total order over distinct h, so the shape of
+// round_best's reduction tree cannot change the winner
+struct RansacBetter {
+    PDSC_DEV bool operator()(const Cand &a, const Cand &b) const {
+        return a.cnt > b.cnt || (a.cnt == b.cnt && (a.s < b.s || (a.s == b.s && a.h < b.h)));
+    }
 };
-// (count desc, sumsq asc, h asc): a total order over distinct h
-PDSC_DEV bool ransac_better(const RansacCand &a, const RansacCand &b) {
-    return a.cnt > b.cnt || (a.cnt == b.cnt && (a.ss < b.ss || (a.ss == b.ss && a.h < b.h)));
-}
 
 __global__ __launch_bounds__(RANSAC_FIN) void ransac_round_kernel(int N, int nwg, int nchunks, int round, int H,
                                                                   int ns, double confidence, RansacBufs B,
                                                                   pdsc_ransac_debug dbg) {
-    __shared__ RansacCand wbest[RANSAC_FIN / 64];
+    __shared__ Cand wbest[RANSAC_FIN / 64];
     RansacState *st = B.st;
     if (st->done) return;  // workgroup-uniform
     const int tid = threadIdx.x;
-    int total = 0;
-    for (int k = 0; k < nwg; ++k) total += B.wgcount[k];
-    RansacCand best = {0.0, -1, 0x7fffffff, 0};
-    for (int g = tid; g < total; g += RANSAC_FIN) {
-        RansacCand x = {0.0, 0, 0, B.gslot[g]};
-        for (int ch = 0; ch < nchunks; ++ch) {  // chunk order
-            x.cnt += B.pcount[(size_t)ch * RANSAC_ROUND + g];
-            x.ss += B.psum[(size_t)ch * RANSAC_ROUND + g];
-        }
-        x.h = B.hidx[x.slot];
-        if (dbg.count) dbg.count[x.h] = x.cnt;
-        if (dbg.sumsq) dbg.sumsq[x.h] = x.ss;
-        if (ransac_better(x, best)) best = x;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        RansacCand y;
-        y.ss = __shfl_xor(best.ss, o);
-        y.cnt = __shfl_xor(best.cnt, o);
-        y.h = __shfl_xor(best.h, o);
-        y.slot = __shfl_xor(best.slot, o);
-        if (ransac_better(y, best)) best = y;
-    }
-    if ((tid & 63) == 0) wbest[tid >> 6] = best;
-    __syncthreads();
+    int total;
+    const Cand best = round_best(B, nwg, nchunks, dbg, Cand{0.0, -1, 0x7fffffff, 0}, wbest, tid, total, RansacBetter{});
     if (tid != 0) return;
-    for (int k = 1; k < RANSAC_FIN / 64; ++k)
-        if (ransac_better(wbest[k], best)) best = wbest[k];
     // an earlier round's winner has the lower h: it keeps an exact tie
-    if (best.cnt >= 0 && (best.cnt > st->count || (best.cnt == st->count && best.ss < st->sumsq))) {
+    if (best.cnt >= 0 && (best.cnt > st->count || (best.cnt == st->count && best.s < st->sumsq))) {
         for (int k = 0; k < 12; ++k) st->c[k] = B.coef[(size_t)k * RANSAC_ROUND + best.slot];
-        st->sumsq = best.ss;
+        st->sumsq = best.s;
         st->count = best.cnt;
         st->best = best.h;
     }
     const long long drawn = ((long long)round + 1) * RANSAC_ROUND;
     st->iterations = drawn < (long long)H ? (int)drawn : H;
     st->n_validated += total;
-    if (confidence < 1.0 && st->count > 0) {
-        bool stop = st->count == N;  // f = 1: the criterion's log(0)
-        if (!stop) {
-            const double f = (double)st->count / (double)N;
-            const double fn = ns == 3 ? f * f * f : (f * f) * (f * f);
-            stop = (double)drawn >= log(1.0 - confidence) / log(1.0 - fn);
-        }
-        if (stop) st->done = 1;
-    }
+    if (confidence_stop(st->count, N, ns, drawn, confidence)) st->done = 1;
 }
 
 // ---------------------------------------------------------------------- finish
@@ -133,26 +98,14 @@ __global__ __launch_bounds__(RANSAC_FIN) void ransac_finish_kernel(const float *
     for (int k = 0; k < 12; ++k) c[k] = st->c[k];
     const bool refit_now = refit && count > 0;  // workgroup-uniform
     double n = 0.0, sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0};
-    for (int i = tid; i < N; i += RANSAC_FIN) {
-        const D3 a = load3(src, i), b = load3(tgt, i);
-        const bool in = count >= 0 && ransac_d2(c, a.x, a.y, a.z, b.x, b.y, b.z) < r2;
-        if (labels) labels[i] = in ? 1.0f : 0.0f;
-        if (in) {
-            n += 1.0;
-            sa[0] += a.x, sa[1] += a.y, sa[2] += a.z;
-            sb[0] += b.x, sb[1] += b.y, sb[2] += b.z;
-        }
-    }
+    label_inliers(src, tgt, N, c, r2, count >= 0, labels, n, sa, sb, tid);
     if (refit_now) {
         n = block_sum(n, red, tid);
         refit_kabsch(src, tgt, N, r2, n, sa, sb, c, red, tid);
     }
     if (tid != 0) return;
     double T[16];
-    T[0] = c[0], T[1] = c[1], T[2] = c[2], T[3] = c[9];
-    T[4] = c[3], T[5] = c[4], T[6] = c[5], T[7] = c[10];
-    T[8] = c[6], T[9] = c[7], T[10] = c[8], T[11] = c[11];
-    T[12] = 0.0, T[13] = 0.0, T[14] = 0.0, T[15] = 1.0;
+    pose16(c, T);
     if (res) {
         for (int i = 0; i < 16; ++i) res->trans[i] = T[i];
         res->fitness = count > 0 ? (double)count / (double)N : 0.0;
@@ -178,28 +131,16 @@ __global__ __launch_bounds__(RANSAC_FIN) void refit_inliers_kernel(const double 
                                                                    float *labels) {
     __shared__ double red[RANSAC_FIN / 64];
     const int tid = threadIdx.x;
-    double T[16];
+    double T[16], c[12];
 #pragma unroll
     for (int k = 0; k < 16; ++k) T[k] = pose[k];
-    double c[12] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10], T[3], T[7], T[11]};
+    pose12(T, c);
     double n = 0.0, sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0};
-    for (int i = tid; i < N; i += RANSAC_FIN) {
-        const D3 a = load3(src, i), b = load3(tgt, i);
-        const bool in = ransac_d2(c, a.x, a.y, a.z, b.x, b.y, b.z) < r2;
-        if (labels) labels[i] = in ? 1.0f : 0.0f;
-        if (in) {
-            n += 1.0;
-            sa[0] += a.x, sa[1] += a.y, sa[2] += a.z;
-            sb[0] += b.x, sb[1] += b.y, sb[2] += b.z;
-        }
-    }
+    label_inliers(src, tgt, N, c, r2, true, labels, n, sa, sb, tid);
     n = block_sum(n, red, tid);  // workgroup-uniform
     if (n >= 3.0) {
         refit_kabsch(src, tgt, N, r2, n, sa, sb, c, red, tid);
-        T[0] = c[0], T[1] = c[1], T[2] = c[2], T[3] = c[9];
-        T[4] = c[3], T[5] = c[4], T[6] = c[5], T[7] = c[10];
-        T[8] = c[6], T[9] = c[7], T[10] = c[8], T[11] = c[11];
-        T[12] = 0.0, T[13] = 0.0, T[14] = 0.0, T[15] = 1.0;
+        pose16(c, T);
     }
     if (tid != 0) return;
     for (int i = 0; i < 16; ++i) trans[i] = T[i];
@@ -217,38 +158,35 @@ hipError_t launch_refit_inliers(const double *pose, const float *src, const floa
 
 // ------------------------------------------------------------------- launchers
 size_t ransac_workspace_bytes(int N) {
-    const size_t R = RANSAC_ROUND;
-    return align_bytes(sizeof(RansacState)) + align_bytes(RANSAC_NWG * sizeof(int)) + 2 * align_bytes(R * sizeof(int)) +
-           align_bytes(12 * R * sizeof(double)) + align_bytes(ransac_chunks(N) * R * sizeof(int)) +
-           align_bytes(ransac_chunks(N) * R * sizeof(double));
+    Carve c(nullptr);
+    RansacBufs B;
+    bind_ransac(c, N, B);
+    return c.off;
 }
 
 hipError_t launch_ransac(const float *src, const float *tgt, int N, double max_distance, int ransac_n, double sim,
                          int H, double confidence, unsigned long long seed, int refit, float *trans_f32, float *labels,
                          pdsc_ransac_result *res, const pdsc_ransac_debug *debug, void *ws, hipStream_t s) {
-    const size_t R = RANSAC_ROUND;
     const int nchunks = (int)ransac_chunks(N);
+    Carve c(ws);
     RansacBufs B;
-    ransac_bind(static_cast<char *>(ws), N, B);
+    bind_ransac(c, N, B);
     pdsc_ransac_debug dbg = {nullptr, nullptr, nullptr, nullptr};
     if (debug) dbg = *debug;
     const double r2 = max_distance * max_distance;
     const int init_blocks = dbg.count ? (int)(((size_t)H + 255) / 256) : 1;
     hipLaunchKernelGGL(ransac_init_kernel, dim3(init_blocks), dim3(256), 0, s, B.st, H, dbg.count);
-    const int rounds = (int)(((size_t)H + R - 1) / R);
-    for (int r = 0; r < rounds; ++r) {
-        const long long base = (long long)r * RANSAC_ROUND;
-        const int nh = (int)((long long)H - base < (long long)R ? (long long)H - base : (long long)R);
-        const int nwg = (nh + RANSAC_HWG - 1) / RANSAC_HWG;
+    for (int r = 0, rounds = ransac_rounds(H); r < rounds; ++r) {
+        const RoundShape q = ransac_round_shape(H, r);
         if (ransac_n == 3)
-            hipLaunchKernelGGL(ransac_hyp_kernel<3>, dim3(nwg), dim3(RANSAC_HWG), 0, s, src, tgt, N, (int)base, H,
+            hipLaunchKernelGGL(ransac_hyp_kernel<3>, dim3(q.nwg), dim3(RANSAC_HWG), 0, s, src, tgt, N, q.base, H,
                                (u64)seed, sim, B, dbg);
         else
-            hipLaunchKernelGGL(ransac_hyp_kernel<4>, dim3(nwg), dim3(RANSAC_HWG), 0, s, src, tgt, N, (int)base, H,
+            hipLaunchKernelGGL(ransac_hyp_kernel<4>, dim3(q.nwg), dim3(RANSAC_HWG), 0, s, src, tgt, N, q.base, H,
                                (u64)seed, sim, B, dbg);
-        hipLaunchKernelGGL(ransac_score_kernel<false>, dim3((nh + 63) / 64, nchunks), dim3(64), 0, s, src, tgt, N, nwg,
-                           r2, B);
-        hipLaunchKernelGGL(ransac_round_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, N, nwg, nchunks, r, H, ransac_n,
+        hipLaunchKernelGGL(ransac_score_kernel<false>, dim3((q.nh + 63) / 64, nchunks), dim3(64), 0, s, src, tgt, N,
+                           q.nwg, r2, B);
+        hipLaunchKernelGGL(ransac_round_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, N, q.nwg, nchunks, r, H, ransac_n,
                            confidence, B, dbg);
         HIP_RET(hipGetLastError());
     }

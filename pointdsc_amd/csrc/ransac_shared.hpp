@@ -1,12 +1,20 @@
-// ransac_shared.hpp -- what ransac.hip (f6) and gc_ransac.hip (f10) share: the
-// counter-based sampler, the fp64 Kabsch of a sample (compensated H, Jacobi SVD,
-// one Newton step), d^2, the hypothesis and scoring kernels (templates: each
-// translation unit instantiates its own) and the refit over a row predicate.
+// ransac_shared.hpp -- what ransac.hip (f6) and gc_ransac.hip (f10) share:
+//   host    the round workspace's layout (bind_ransac) and a round's launch shape
+//           (ransac_round_shape);
+//   sample  the counter-based sampler, the fp64 Kabsch of a sample (compensated H,
+//           Jacobi SVD, one Newton step), d^2, the c[12] <-> T[16] pose conversions;
+//   round   the hypothesis and scoring kernels (templates: each translation unit
+//           instantiates its own), the "never drawn" debug prefill, the round's
+//           reduction under a caller's total order (round_best) and the
+//           confidence stop rule;
+//   finish  the label-and-sum loop over d^2 < r2 (label_inliers) and the refit
+//           over a row predicate.
 // Everything here is fp64 without contraction in a fixed order, so a caller
 // gets the same bits from either translation unit.
 #pragma once
 #include "pdsc_common.hpp"
 #include "pdsc_internal.hpp"
+#include "workspace.hpp"
 
 namespace pdsc {
 
@@ -34,23 +42,28 @@ struct RansacBufs {
     double *psum;  // [nchunks][ROUND]
 };
 
-// the workspace of a round: ransac_workspace_bytes(N) bytes from w on; returns their end
+// the workspace of a round over N rows
 inline size_t ransac_chunks(int N) { return ((size_t)N + RANSAC_PCHUNK - 1) / RANSAC_PCHUNK; }
-inline char *ransac_bind(char *w, int N, RansacBufs &B) {
+inline void bind_ransac(Carve &c, int N, RansacBufs &B) {
     const size_t R = RANSAC_ROUND, nchunks = ransac_chunks(N);
-    auto take = [&w](size_t bytes) {
-        char *p = w;
-        w += align_bytes(bytes);
-        return p;
-    };
-    B.st = reinterpret_cast<RansacState *>(take(sizeof(RansacState)));
-    B.wgcount = reinterpret_cast<int *>(take(RANSAC_NWG * sizeof(int)));
-    B.hidx = reinterpret_cast<int *>(take(R * sizeof(int)));
-    B.gslot = reinterpret_cast<int *>(take(R * sizeof(int)));
-    B.coef = reinterpret_cast<double *>(take(12 * R * sizeof(double)));
-    B.pcount = reinterpret_cast<int *>(take(nchunks * R * sizeof(int)));
-    B.psum = reinterpret_cast<double *>(take(nchunks * R * sizeof(double)));
-    return w;
+    B.st = c.take<RansacState>(1);
+    B.wgcount = c.take<int>(RANSAC_NWG);
+    B.hidx = c.take<int>(R);
+    B.gslot = c.take<int>(R);
+    B.coef = c.take<double>(12 * R);
+    B.pcount = c.take<int>(nchunks * R);
+    B.psum = c.take<double>(nchunks * R);
+}
+
+// Round r of H hypotheses: the first hypothesis, how many it draws, their workgroups.
+struct RoundShape {
+    int base, nh, nwg;
+};
+inline int ransac_rounds(int H) { return (int)(((size_t)H + RANSAC_ROUND - 1) / RANSAC_ROUND); }
+inline RoundShape ransac_round_shape(int H, int r) {
+    const long long base = (long long)r * RANSAC_ROUND, left = (long long)H - base;
+    const int nh = (int)(left < (long long)RANSAC_ROUND ? left : (long long)RANSAC_ROUND);
+    return {(int)base, nh, (nh + RANSAC_HWG - 1) / RANSAC_HWG};
 }
 
 PDSC_DEV u64 mix64(u64 z) {  // the splitmix64 finaliser
@@ -150,6 +163,21 @@ PDSC_DEV void kabsch_pose(const double R[9], const D3 &ca, const D3 &cb, double 
     c[9] = cb.x - ((R[0] * ca.x + R[1] * ca.y) + R[2] * ca.z);
     c[10] = cb.y - ((R[3] * ca.x + R[4] * ca.y) + R[5] * ca.z);
     c[11] = cb.z - ((R[6] * ca.x + R[7] * ca.y) + R[8] * ca.z);
+}
+
+// c = R row-major [9], t [3]  <->  T = the row-major 4x4 (its last row 0 0 0 1)
+PDSC_DEV void pose16(const double c[12], double T[16]) {
+    T[0] = c[0], T[1] = c[1], T[2] = c[2], T[3] = c[9];
+    T[4] = c[3], T[5] = c[4], T[6] = c[5], T[7] = c[10];
+    T[8] = c[6], T[9] = c[7], T[10] = c[8], T[11] = c[11];
+    T[12] = 0.0, T[13] = 0.0, T[14] = 0.0, T[15] = 1.0;
+}
+PDSC_DEV void pose12(const double T[16], double c[12]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        c[3 * i] = T[4 * i], c[3 * i + 1] = T[4 * i + 1], c[3 * i + 2] = T[4 * i + 2];
+        c[9 + i] = T[4 * i + 3];
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -369,13 +397,7 @@ __global__ __launch_bounds__(RANSAC_HWG) void ransac_hyp_kernel(const float *__r
     B.hidx[slot] = hh;
 #pragma unroll
     for (int k = 0; k < 12; ++k) B.coef[(size_t)k * RANSAC_ROUND + slot] = c[k];
-    if (dbg.trans) {
-        double *T = dbg.trans + (size_t)hh * 16;
-        T[0] = c[0], T[1] = c[1], T[2] = c[2], T[3] = c[9];
-        T[4] = c[3], T[5] = c[4], T[6] = c[5], T[7] = c[10];
-        T[8] = c[6], T[9] = c[7], T[10] = c[8], T[11] = c[11];
-        T[12] = 0.0, T[13] = 0.0, T[14] = 0.0, T[15] = 1.0;
-    }
+    if (dbg.trans) pose16(c, dbg.trans + (size_t)hh * 16);
 }
 
 // ----------------------------------------------------------------------- score
@@ -450,7 +472,84 @@ __global__ __launch_bounds__(64) void ransac_score_kernel(const float *__restric
     }
 }
 
+// ----------------------------------------------------------------------- round
+// The debug rows' "never drawn" status, by the init kernels' 256-thread
+// workgroups (the rounds after an early stop return at entry and cannot write it).
+PDSC_DEV void debug_prefill(int *dbg_count, int H, size_t i) {
+    if (dbg_count && i < (size_t)H) dbg_count[i] = -3;
+}
+
+struct Cand {  // a scored hypothesis: its score (sum d^2, or the MSAC sum), inlier count, h and coefficient slot
+    double s;
+    int cnt, h, slot;
+};
+
+// The round's winner under `better`, returned to thread 0 (the other threads'
+// return value is their wave's): the survivors' chunk rows added in chunk order
+// (and written to the debug rows), a strided scan, the xor butterfly, then the
+// waves through wbest [RANSAC_FIN / 64].  `better` must be a total order over
+// distinct h, so that neither the stride nor the tree's shape can change the
+// winner; `identity` loses to every candidate.  Sets total = the survivors.
+template <typename Better>
+PDSC_DEV Cand round_best(const RansacBufs &B, int nwg, int nchunks, const pdsc_ransac_debug &dbg, Cand identity,
+                         Cand *wbest, int tid, int &total, Better better) {
+    total = 0;
+    for (int k = 0; k < nwg; ++k) total += B.wgcount[k];
+    Cand best = identity;
+    for (int g = tid; g < total; g += RANSAC_FIN) {
+        Cand x = {0.0, 0, 0, B.gslot[g]};
+        for (int ch = 0; ch < nchunks; ++ch) {  // chunk order
+            x.cnt += B.pcount[(size_t)ch * RANSAC_ROUND + g];
+            x.s += B.psum[(size_t)ch * RANSAC_ROUND + g];
+        }
+        x.h = B.hidx[x.slot];
+        if (dbg.count) dbg.count[x.h] = x.cnt;
+        if (dbg.sumsq) dbg.sumsq[x.h] = x.s;
+        if (better(x, best)) best = x;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        Cand y;
+        y.s = __shfl_xor(best.s, o);
+        y.cnt = __shfl_xor(best.cnt, o);
+        y.h = __shfl_xor(best.h, o);
+        y.slot = __shfl_xor(best.slot, o);
+        if (better(y, best)) best = y;
+    }
+    if ((tid & 63) == 0) wbest[tid >> 6] = best;
+    __syncthreads();
+    if (tid != 0) return best;
+    for (int k = 1; k < RANSAC_FIN / 64; ++k)
+        if (better(wbest[k], best)) best = wbest[k];
+    return best;
+}
+
+// The confidence stop after `drawn` hypotheses of ns points with `count` of N rows inliers of the best.
+PDSC_DEV bool confidence_stop(int count, int N, int ns, long long drawn, double confidence) {
+    if (!(confidence < 1.0 && count > 0)) return false;
+    if (count == N) return true;  // f = 1: the criterion's log(0)
+    const double f = (double)count / (double)N;
+    const double fn = ns == 3 ? f * f * f : (f * f) * (f * f);
+    return (double)drawn >= log(1.0 - confidence) / log(1.0 - fn);
+}
+
 // ---------------------------------------------------------------------- finish
+// labels[i] = d^2 < r2 under c (all 0 unless valid; labels may be null), and this
+// thread's inlier count and coordinate sums over its rows tid, tid + RANSAC_FIN, ...
+PDSC_DEV void label_inliers(const float *__restrict__ src, const float *__restrict__ tgt, int N, const double c[12],
+                            double r2, bool valid, float *labels, double &n, double sa[3], double sb[3], int tid) {
+    for (int i = tid; i < N; i += RANSAC_FIN) {
+        const D3 a = load3(src, i), b = load3(tgt, i);
+        const bool in = valid && ransac_d2(c, a.x, a.y, a.z, b.x, b.y, b.z) < r2;
+        if (labels) labels[i] = in ? 1.0f : 0.0f;
+        if (in) {
+            n += 1.0;
+            sa[0] += a.x, sa[1] += a.y, sa[2] += a.z;
+            sb[0] += b.x, sb[1] += b.y, sb[2] += b.z;
+        }
+    }
+}
+
 // Sum of v over the workgroup in a fixed order (xor butterfly, then the waves in
 // order); every thread returns the same bits.  red: [RANSAC_FIN / 64].
 PDSC_DEV double block_sum(double v, double *red, int tid) {

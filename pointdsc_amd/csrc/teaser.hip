@@ -13,6 +13,7 @@
 // partials in wave order), no atomics: two calls are bitwise equal.
 // DESIGN.md §7 "TEASER++" has the shapes and the numbers.
 #include "pdsc_internal.hpp"
+#include "workspace.hpp"
 
 #pragma clang fp contract(off)
 
@@ -429,36 +430,29 @@ struct TeaserWs {
     pdsc_gnc_info *info;
     double *A, *B, *S, *D, *R, *t, *pre;
     void *clique;
-    size_t bytes;
 };
 
-TeaserWs carve_teaser(void *ws, int N) {
+double *carve_tls(Carve &c, int K) { return c.take<double>((size_t)3 * 2 * ((size_t)K + 1)); }
+
+TeaserWs carve_teaser(Carve &k, int N) {
     const int W = (N + 63) / 64;
-    char *base = static_cast<char *>(ws);
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char *p = base ? base + off : nullptr;
-        off += align_bytes(n);
-        return p;
-    };
     TeaserWs c;
-    c.corr = reinterpret_cast<float *>(take((size_t)N * 6 * 4));
-    c.adj = reinterpret_cast<unsigned long long *>(take((size_t)N * W * 8));
-    c.members = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.kdev = reinterpret_cast<int *>(take(4));
-    c.rinl = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.tinl = reinterpret_cast<int *>(take((size_t)N * 4));
-    c.cr = reinterpret_cast<pdsc_clique_result *>(take(sizeof(pdsc_clique_result)));
-    c.info = reinterpret_cast<pdsc_gnc_info *>(take(sizeof(pdsc_gnc_info)));
-    c.A = reinterpret_cast<double *>(take((size_t)N * 24));
-    c.B = reinterpret_cast<double *>(take((size_t)N * 24));
-    c.S = reinterpret_cast<double *>(take((size_t)N * 24));
-    c.D = reinterpret_cast<double *>(take((size_t)N * 24));
-    c.R = reinterpret_cast<double *>(take(9 * 8));
-    c.t = reinterpret_cast<double *>(take(3 * 8));
-    c.pre = reinterpret_cast<double *>(take(tls_workspace_bytes(N)));
-    c.clique = take(clique_workspace_bytes(N));
-    c.bytes = off;
+    c.corr = k.take<float>((size_t)N * 6);
+    c.adj = k.take<unsigned long long>((size_t)N * W);
+    c.members = k.take<int>((size_t)N);
+    c.kdev = k.take<int>(1);
+    c.rinl = k.take<int>((size_t)N);
+    c.tinl = k.take<int>((size_t)N);
+    c.cr = k.take<pdsc_clique_result>(1);
+    c.info = k.take<pdsc_gnc_info>(1);
+    c.A = k.take<double>((size_t)N * 3);
+    c.B = k.take<double>((size_t)N * 3);
+    c.S = k.take<double>((size_t)N * 3);
+    c.D = k.take<double>((size_t)N * 3);
+    c.R = k.take<double>(9);
+    c.t = k.take<double>(3);
+    c.pre = carve_tls(k, N);
+    c.clique = reserve_clique(k, N);
     return c;
 }
 
@@ -483,24 +477,33 @@ hipError_t launch_gnc_rotation(const double *A, const double *B, int K, const in
     return hipGetLastError();
 }
 
-size_t tls_workspace_bytes(int K) { return align_bytes((size_t)3 * 2 * ((size_t)K + 1) * sizeof(double)); }
+size_t tls_workspace_bytes(int K) {
+    Carve c(nullptr);
+    carve_tls(c, K);
+    return c.off;
+}
 
 hipError_t launch_tls_translation(const double *src, const double *dst, int K, const int *Kdev, double noise_bound,
                                   double *t, int *inliers, void *ws, hipStream_t s) {
-    hipLaunchKernelGGL(tls_axis_kernel, dim3(3), dim3(TB), 0, s, src, dst, K, Kdev, noise_bound,
-                       static_cast<double *>(ws), K, t);
+    Carve c(ws);
+    hipLaunchKernelGGL(tls_axis_kernel, dim3(3), dim3(TB), 0, s, src, dst, K, Kdev, noise_bound, carve_tls(c, K), K, t);
     if (inliers)
         hipLaunchKernelGGL(tls_inlier_kernel, dim3((K + 255) / 256), dim3(256), 0, s, src, dst, K, Kdev, noise_bound, t,
                            inliers);
     return hipGetLastError();
 }
 
-size_t teaser_workspace_bytes(int N) { return carve_teaser(nullptr, N).bytes; }
+size_t teaser_workspace_bytes(int N) {
+    Carve k(nullptr);
+    carve_teaser(k, N);
+    return k.off;
+}
 
 hipError_t launch_teaser_solve(const float *src, const float *tgt, int N, double noise_bound, double factor,
                                int max_iter, double cost_thr, long long budget, pdsc_teaser_result *res,
                                float *trans_f32, float *labels, void *ws, hipStream_t s) {
-    const TeaserWs c = carve_teaser(ws, N);
+    Carve k(ws);
+    const TeaserWs c = carve_teaser(k, N);
     const dim3 rows((N + 255) / 256), b256(256);
     hipLaunchKernelGGL(pack_kernel, rows, b256, 0, s, src, tgt, N, c.corr);
     HIP_RET(launch_consistency_graph(c.corr, N, 2.0 * noise_bound, true, c.adj, nullptr, s));
