@@ -32,6 +32,7 @@ import torch.nn as nn
 from torch.nn.modules import module as _nn_module
 
 from . import _lib, kernels
+from ._call import query
 
 # Bumped whenever ANY module registers (or replaces) a parameter, buffer or
 # sub-module -- e.g. ``model.encoder.layer0.weight = nn.Parameter(...)``: every
@@ -265,7 +266,7 @@ class PointDSC(nn.Module):
     def _workspace(self, cfg, B, N, device):
         """The forward's workspace for (cfg, B, N) on the current stream, cached
         per stream (stream order keeps consecutive forwards apart)."""
-        nb = _lib.load().pdsc_forward_workspace_bytes(ctypes.byref(cfg), B, N)
+        nb = query("pdsc_forward_workspace_bytes", cfg, B, N)
         if nb == 0 or nb > _WS_CACHE_LIMIT:
             return None  # forward_testing allocates (or reports the unsupported configuration)
         key = (device, torch.cuda.current_stream(device).cuda_stream)

@@ -55,6 +55,18 @@ class PdscForwardDebug(ctypes.Structure):
     _fields_ = [("conf", vp), ("seeds", vp), ("knn", vp), ("weights", vp), ("trans_pre_refine", vp)]
 
 
+class PdscIcpResult(ctypes.Structure):
+    """``struct pdsc_icp_result`` (include/pdsc.h): 152 bytes of device memory."""
+    _fields_ = [("trans", c_double * 16), ("fitness", c_double), ("inlier_rmse", c_double), ("iterations", c_int32),
+                ("n_corr", c_int32)]
+
+
+class PdscRansacResult(ctypes.Structure):
+    """``struct pdsc_ransac_result`` (include/pdsc.h): 160 bytes of device memory."""
+    _fields_ = [("trans", c_double * 16), ("fitness", c_double), ("inlier_rmse", c_double), ("n_inliers", c_int32),
+                ("iterations", c_int32), ("best", c_int32), ("n_validated", c_int32)]
+
+
 class PdscRansacDebug(ctypes.Structure):
     """``struct pdsc_ransac_debug`` (include/pdsc.h): optional per-hypothesis outputs."""
     _fields_ = [("samples", vp), ("count", vp), ("sumsq", vp), ("trans", vp)]

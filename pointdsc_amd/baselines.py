@@ -12,9 +12,8 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
-from ._lib import check
-from .kernels import _dev, _p, _stream, _workspace
+from ._call import call
+from .kernels import _dev
 
 
 def SM(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, top_ratio: float = 0.1,
@@ -25,15 +24,11 @@ def SM(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, top_ratio: 
     if corr.shape != (1, N, 6) or src.shape != (1, N, 3) or tgt.shape != (1, N, 3):
         raise ValueError(f"shapes {tuple(corr.shape)} {tuple(src.shape)} {tuple(tgt.shape)}")
     dev = corr.device
-    L = _lib.load()
-    nb = L.pdsc_spectral_matching_workspace_bytes(N)
-    ws = _workspace(nb, dev)
     trans = torch.empty((1, 4, 4), dtype=torch.float32, device=dev)
     labels = torch.empty((1, N), dtype=torch.float32, device=dev)
     eig = torch.empty((1, N), dtype=torch.float32, device=dev)
-    check(L.pdsc_spectral_matching(_p(corr), _p(src), _p(tgt), N, float(inlier_threshold), float(top_ratio),
-                                   int(num_iterations), _p(trans), _p(labels), _p(eig), _p(ws), nb, _stream(dev)),
-          "pdsc_spectral_matching")
+    call("pdsc_spectral_matching", corr, src, tgt, N, float(inlier_threshold), float(top_ratio), int(num_iterations),
+         trans, labels, eig, device=dev, ws=("pdsc_spectral_matching_workspace_bytes", N))
     return (trans, labels, eig) if return_eig else (trans, labels)
 
 
@@ -110,5 +105,5 @@ def sm_matvec(M, v):
     M, v = _dev(M, "M"), _dev(v, "v")
     N = v.shape[0]
     y = torch.empty(N, dtype=torch.float32, device=v.device)
-    check(_lib.load().pdsc_sm_matvec(_p(M), _p(v), N, _p(y), _stream(v.device)), "pdsc_sm_matvec")
+    call("pdsc_sm_matvec", M, v, N, y, device=v.device)
     return y

@@ -20,9 +20,8 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
-from ._lib import check
-from .kernels import _dev, _p, _stream, _workspace
+from ._call import call
+from .kernels import _dev
 
 
 def mutual_nn(src_desc: torch.Tensor, tgt_desc: torch.Tensor):
@@ -32,13 +31,9 @@ def mutual_nn(src_desc: torch.Tensor, tgt_desc: torch.Tensor):
     (Ns, D), Nt = a.shape, b.shape[0]
     if b.shape[1] != D:
         raise ValueError(f"descriptor widths differ: {D} vs {b.shape[1]}")
-    L = _lib.load()
-    nb = L.pdsc_mutual_nn_workspace_bytes(Ns, Nt)
-    ws = _workspace(nb, a.device)
     si = torch.empty(Ns, dtype=torch.int32, device=a.device)
     ti = torch.empty(Nt, dtype=torch.int32, device=a.device)
-    check(L.pdsc_mutual_nn(_p(a), _p(b), Ns, Nt, D, _p(si), _p(ti), _p(ws), nb, _stream(a.device)),
-          "pdsc_mutual_nn")
+    call("pdsc_mutual_nn", a, b, Ns, Nt, D, si, ti, device=a.device, ws=("pdsc_mutual_nn_workspace_bytes", Ns, Nt))
     return si, ti
 
 
@@ -63,18 +58,14 @@ def build_correspondences(src_keypts: torch.Tensor, tgt_keypts: torch.Tensor, sr
     gt = None
     if gt_trans is not None:
         gt = torch.as_tensor(gt_trans).to(device=dev, dtype=torch.float64).reshape(4, 4).contiguous()
-    L = _lib.load()
-    nb = L.pdsc_mutual_nn_workspace_bytes(Ns, Nt)
-    ws = _workspace(nb, dev)
     corr = torch.empty((Ns, 2), dtype=torch.int32, device=dev)
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     corr_pos = torch.empty((Ns, 6), dtype=torch.float32, device=dev)
     so = torch.empty((Ns, 3), dtype=torch.float32, device=dev)
     to = torch.empty((Ns, 3), dtype=torch.float32, device=dev)
     labels = torch.empty(Ns, dtype=torch.float32, device=dev) if gt is not None else None
-    check(L.pdsc_build_correspondences(_p(a), _p(b), _p(sk), _p(tk), Ns, Nt, D, int(bool(use_mutual)), _p(gt),
-                                       float(inlier_threshold), _p(corr), _p(count), _p(corr_pos), _p(so), _p(to),
-                                       _p(labels), _p(ws), nb, _stream(dev)), "pdsc_build_correspondences")
+    call("pdsc_build_correspondences", a, b, sk, tk, Ns, Nt, D, int(bool(use_mutual)), gt, float(inlier_threshold),
+         corr, count, corr_pos, so, to, labels, device=dev, ws=("pdsc_mutual_nn_workspace_bytes", Ns, Nt))
     n = int(count.item())
     out = {"corr": corr[:n].long(), "corr_pos": corr_pos[:n], "src_keypts": so[:n], "tgt_keypts": to[:n]}
     if labels is not None:

@@ -14,9 +14,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import check
-from .kernels import _dev, _p, _stream, _workspace
+from ._call import call
+from .kernels import _dev
 
 FPFH_DIM = 33
 
@@ -24,12 +23,10 @@ FPFH_DIM = 33
 def read_ply(path: str) -> np.ndarray:
     """o3d.io.read_point_cloud(path).points as float32 [n,3] host memory (binary
     little-endian or ascii PLY, vertex x/y/z)."""
-    L = _lib.load()
     n = ctypes.c_int64()
-    check(L.pdsc_ply_read_xyz(str(path).encode(), None, 0, ctypes.byref(n)), "pdsc_ply_read_xyz")
+    call("pdsc_ply_read_xyz", str(path).encode(), None, 0, n, device=None)
     out = np.empty((n.value, 3), np.float32)
-    check(L.pdsc_ply_read_xyz(str(path).encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)),
-          "pdsc_ply_read_xyz")
+    call("pdsc_ply_read_xyz", str(path).encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, n, device=None)
     return out
 
 
@@ -39,14 +36,11 @@ def radius_knn(points: torch.Tensor, radius: float, max_nn: int):
     the point itself first, -1 padded."""
     points = _dev(points, "points")
     n = points.shape[0]
-    L = _lib.load()
-    nb = L.pdsc_radius_knn_workspace_bytes(n)
-    ws = _workspace(nb, points.device)
     nbr = torch.empty((n, max_nn), dtype=torch.int32, device=points.device)
     d2 = torch.empty((n, max_nn), dtype=torch.float64, device=points.device)
     cnt = torch.empty((n,), dtype=torch.int32, device=points.device)
-    check(L.pdsc_radius_knn(_p(points), n, float(radius), int(max_nn), _p(nbr), _p(d2), _p(cnt), _p(ws), nb,
-                            _stream(points.device)), "pdsc_radius_knn")
+    call("pdsc_radius_knn", points, n, float(radius), int(max_nn), nbr, d2, cnt, device=points.device,
+         ws=("pdsc_radius_knn_workspace_bytes", n))
     return nbr, d2, cnt
 
 
@@ -67,15 +61,12 @@ def estimate_normals(points: torch.Tensor, radius: float, max_nn: int = 30, view
     if orient == "viewpoint" and viewpoint is None:
         raise ValueError("orient='viewpoint' needs a viewpoint")
     n = points.shape[0]
-    L = _lib.load()
-    nb = L.pdsc_estimate_normals_workspace_bytes(n, int(max_nn))
-    ws = _workspace(nb, points.device)
     vp = None
     if viewpoint is not None:
         vp = torch.as_tensor(np.asarray(viewpoint, np.float32).reshape(3), device=points.device)
     out = torch.empty_like(points)
-    check(L.pdsc_estimate_normals(_p(points), n, float(radius), int(max_nn), ORIENT[orient], _p(vp), _p(out), _p(ws),
-                                  nb, _stream(points.device)), "pdsc_estimate_normals")
+    call("pdsc_estimate_normals", points, n, float(radius), int(max_nn), ORIENT[orient], vp, out,
+         device=points.device, ws=("pdsc_estimate_normals_workspace_bytes", n, int(max_nn)))
     return out
 
 
@@ -88,14 +79,11 @@ def voxel_down_sample(points: torch.Tensor, voxel_size: float, normals: torch.Te
         normals = _dev(normals, "normals")
         if normals.shape != points.shape:
             raise ValueError(f"normals {tuple(normals.shape)} != points {tuple(points.shape)}")
-    L = _lib.load()
-    nb = L.pdsc_voxel_down_sample_workspace_bytes(n)
-    ws = _workspace(nb, points.device)
     op = torch.empty_like(points)
     on = torch.empty_like(points) if normals is not None else None
     cnt = torch.empty((1,), dtype=torch.int32, device=points.device)
-    check(L.pdsc_voxel_down_sample(_p(points), _p(normals), n, float(voxel_size), _p(op), _p(on), _p(cnt), _p(ws),
-                                   nb, _stream(points.device)), "pdsc_voxel_down_sample")
+    call("pdsc_voxel_down_sample", points, normals, n, float(voxel_size), op, on, cnt, device=points.device,
+         ws=("pdsc_voxel_down_sample_workspace_bytes", n))
     m = int(cnt.item())
     return op[:m], (on[:m] if on is not None else None)
 
@@ -108,13 +96,10 @@ def compute_fpfh(points: torch.Tensor, normals: torch.Tensor, radius: float, max
     if normals.shape != points.shape:
         raise ValueError(f"normals {tuple(normals.shape)} != points {tuple(points.shape)}")
     n = points.shape[0]
-    L = _lib.load()
-    nb = L.pdsc_compute_fpfh_workspace_bytes(n, int(max_nn))
-    ws = _workspace(nb, points.device)
     f = torch.empty((n, FPFH_DIM), dtype=torch.float64, device=points.device)
     fn = torch.empty((n, FPFH_DIM), dtype=torch.float32, device=points.device)
-    check(L.pdsc_compute_fpfh(_p(points), _p(normals), n, float(radius), int(max_nn), _p(f), _p(fn), _p(ws), nb,
-                              _stream(points.device)), "pdsc_compute_fpfh")
+    call("pdsc_compute_fpfh", points, normals, n, float(radius), int(max_nn), f, fn, device=points.device,
+         ws=("pdsc_compute_fpfh_workspace_bytes", n, int(max_nn)))
     return f, fn
 
 

@@ -16,15 +16,14 @@ There is no CPU path: tensors must be HIP device tensors.
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from time import time
 
 import torch
 
 from . import _lib
-from ._lib import check
-from .kernels import _dev, _p, _stream, _workspace
+from ._call import _p, call, read_struct, struct_buffer, trans_view
+from .kernels import _dev
 
 NEIGHBORHOOD_SIZE = 20  # GC_RANSAC.py:21
 
@@ -76,15 +75,12 @@ def gc_grid(src: torch.Tensor, tgt: torch.Tensor, neighborhood_size: int = NEIGH
     Two rows are neighbours iff they are in the same cell."""
     src, tgt = _pairs(src, tgt)
     n, dev = src.shape[0], src.device
-    L = _lib.load()
-    nb = L.pdsc_gc_grid_workspace_bytes(n)
-    ws = _workspace(nb, dev)
     order = torch.empty(n, dtype=torch.int32, device=dev)
     cell_start = torch.zeros(n + 1, dtype=torch.int32, device=dev)
     cell_of = torch.empty(n, dtype=torch.int32, device=dev)
     n_cells = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(L.pdsc_gc_grid(_p(src), _p(tgt), n, int(neighborhood_size), _p(order), _p(cell_start), _p(cell_of),
-                         _p(n_cells), _p(ws), nb, _stream(dev)), "pdsc_gc_grid")
+    call("pdsc_gc_grid", src, tgt, n, int(neighborhood_size), order, cell_start, cell_of, n_cells, device=dev,
+         ws=("pdsc_gc_grid_workspace_bytes", n))
     return order, cell_start, cell_of, n_cells
 
 
@@ -102,22 +98,17 @@ def gc_label(pose: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, grid, thr
     n, dev = src.shape[0], src.device
     if order.shape != (n,) or cell_start.shape != (n + 1,):
         raise ValueError("grid does not belong to these rows")
-    L = _lib.load()
-    nb = L.pdsc_gc_label_workspace_bytes(n)
-    ws = _workspace(nb, dev)
     labels = torch.empty(n, dtype=torch.float32, device=dev)
     count = torch.zeros(1, dtype=torch.int32, device=dev)
-    dbg, dstruct = None, None
+    dbg = dstruct = None
     if debug:
         dbg = dict(d2=torch.zeros(n, dtype=torch.float64, device=dev),
                    m_star=torch.zeros(n, dtype=torch.int32, device=dev),
                    energy=torch.zeros(n, dtype=torch.float64, device=dev),
                    energy_gap=torch.zeros(n, dtype=torch.float64, device=dev))
-        dstruct = ctypes.byref(_lib.PdscGcLabelDebug(_p(dbg["d2"]), _p(dbg["m_star"]), _p(dbg["energy"]),
-                                                     _p(dbg["energy_gap"])))
-    check(L.pdsc_gc_label(_p(pose), _p(src), _p(tgt), n, _p(order), _p(cell_start), _p(n_cells), float(threshold),
-                          float(spatial_coherence_weight), _p(labels), _p(count), dstruct, _p(ws), nb, _stream(dev)),
-          "pdsc_gc_label")
+        dstruct = _lib.PdscGcLabelDebug(*(_p(dbg[k]) for k in ("d2", "m_star", "energy", "energy_gap")))
+    call("pdsc_gc_label", pose, src, tgt, n, order, cell_start, n_cells, float(threshold),
+         float(spatial_coherence_weight), labels, count, dstruct, device=dev, ws=("pdsc_gc_label_workspace_bytes", n))
     return (labels, count, dbg) if debug else (labels, count)
 
 
@@ -131,28 +122,22 @@ def gc_ransac(src: torch.Tensor, tgt: torch.Tensor, threshold: float, spatial_co
     bitwise equal."""
     src, tgt = _pairs(src, tgt)
     n, dev, H = src.shape[0], src.device, int(max_iteration)
-    L = _lib.load()
-    nb = L.pdsc_gc_ransac_workspace_bytes(n)
-    ws = _workspace(nb, dev)
-    res = torch.empty(20, dtype=torch.float64, device=dev)  # struct pdsc_gc_ransac_result
+    res = struct_buffer(_lib.PdscGcRansacResult, dev)
     t32 = torch.empty((4, 4), dtype=torch.float32, device=dev)
     labels = torch.empty(n, dtype=torch.float32, device=dev)
-    dbg, dstruct = None, None
+    dbg = dstruct = None
     if debug and H >= 1:
         dbg = dict(samples=torch.zeros((H, 3), dtype=torch.int32, device=dev),
                    count=torch.zeros(H, dtype=torch.int32, device=dev),
                    score=torch.zeros(H, dtype=torch.float64, device=dev),
                    trans=torch.zeros((H, 4, 4), dtype=torch.float64, device=dev))
-        dstruct = ctypes.byref(_lib.PdscGcRansacDebug(_p(dbg["samples"]), _p(dbg["count"]), _p(dbg["score"]),
-                                                      _p(dbg["trans"])))
-    check(L.pdsc_gc_ransac(_p(src), _p(tgt), n, float(threshold), float(spatial_coherence_weight),
-                           int(neighborhood_size), H, float(confidence), int(seed) & (2 ** 64 - 1),
-                           1 if local_optimization else 0, _p(t32), _p(labels), _p(res), dstruct, _p(ws), nb,
-                           _stream(dev)), "pdsc_gc_ransac")
-    tail = res[16:].cpu()
-    counts = tail[1:].view(torch.int32)
-    return GcRansacResult(res[:16].view(4, 4), t32, labels, int(counts[0]), float(tail[0]), int(counts[1]),
-                          int(counts[2]), int(counts[3]), int(counts[4]), int(counts[5]), dbg)
+        dstruct = _lib.PdscGcRansacDebug(*(_p(dbg[k]) for k in ("samples", "count", "score", "trans")))
+    call("pdsc_gc_ransac", src, tgt, n, float(threshold), float(spatial_coherence_weight), int(neighborhood_size), H,
+         float(confidence), int(seed) & (2 ** 64 - 1), 1 if local_optimization else 0, t32, labels, res, dstruct,
+         device=dev, ws=("pdsc_gc_ransac_workspace_bytes", n))
+    r = read_struct(res, _lib.PdscGcRansacResult)
+    return GcRansacResult(trans_view(res), t32, labels, r.n_inliers, r.score, r.iterations, r.best, r.lo_runs,
+                          r.lo_steps, r.n_cells, dbg)
 
 
 def GC_RANSAC(A, B, distance_threshold, num_iterations, args, match_quality, seed=0):

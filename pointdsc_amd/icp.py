@@ -14,8 +14,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import check
-from .kernels import _dev, _p, _stream, _workspace
+from ._call import call, read_struct, struct_buffer, trans_view
+from .kernels import _dev
 
 
 @dataclass
@@ -52,19 +52,14 @@ def registration_icp(source: torch.Tensor, target: torch.Tensor, max_distance: f
             raise TypeError(f"init must be a [4,4] float32 / float64 tensor, got {init.dtype} {tuple(init.shape)}")
         init = init.to(torch.float64).contiguous()
     ns, nt = source.shape[0], target.shape[0]
-    L = _lib.load()
-    nb = L.pdsc_icp_workspace_bytes(ns, nt)
-    ws = _workspace(nb, dev)
-    res = torch.empty(19, dtype=torch.float64, device=dev)  # struct pdsc_icp_result
+    res = struct_buffer(_lib.PdscIcpResult, dev)
     t32 = torch.empty((4, 4), dtype=torch.float32, device=dev)
     corr = torch.empty(ns, dtype=torch.int32, device=dev) if want_correspondences else None
-    check(L.pdsc_icp_point_to_point(_p(source), ns, _p(target), nt, _p(init), float(max_distance), int(max_iteration),
-                                    float(relative_fitness), float(relative_rmse), _p(t32), _p(res), _p(corr), _p(ws),
-                                    nb, _stream(dev)), "pdsc_icp_point_to_point")
-    tail = res[16:].cpu()
-    counts = tail[2:].view(torch.int32)
-    return RegistrationResult(res[:16].view(4, 4), t32, float(tail[0]), float(tail[1]), int(counts[0]),
-                              int(counts[1]), corr)
+    call("pdsc_icp_point_to_point", source, ns, target, nt, init, float(max_distance), int(max_iteration),
+         float(relative_fitness), float(relative_rmse), t32, res, corr, device=dev,
+         ws=("pdsc_icp_workspace_bytes", ns, nt))
+    r = read_struct(res, _lib.PdscIcpResult)
+    return RegistrationResult(trans_view(res), t32, r.fitness, r.inlier_rmse, r.iterations, r.n_corr, corr)
 
 
 def icp_refine(src_keypts: torch.Tensor, tgt_keypts: torch.Tensor, pred_trans: torch.Tensor,

@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._call import _p, _stream, _workspace, call, query, read_struct, struct_buffer, trans_view  # noqa: F401
 from ._lib import check
 
 CH = 128
@@ -28,18 +29,6 @@ def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     return t.contiguous()
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(device=None):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _workspace(nbytes: int, device) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-
-
 # --------------------------------------------------------------------- a1
 def compat(src: torch.Tensor, tgt: torch.Tensor, sigma_d: torch.Tensor) -> torch.Tensor:
     """M [B,N,N] (models/PointDSC.py:150-153).  src/tgt [B,N,3]; sigma_d: device scalar tensor."""
@@ -47,8 +36,7 @@ def compat(src: torch.Tensor, tgt: torch.Tensor, sigma_d: torch.Tensor) -> torch
     sigma_d = _dev(sigma_d.reshape(-1), "sigma_d")
     B, N, _ = src.shape
     M = torch.empty((B, N, N), dtype=torch.float32, device=src.device)
-    check(_lib.load().pdsc_compat_f32(_p(src), _p(tgt), B, N, _p(sigma_d), _p(M), _stream(src.device)),
-          "pdsc_compat_f32")
+    call("pdsc_compat_f32", src, tgt, B, N, sigma_d, M, device=src.device)
     return M
 
 
@@ -58,11 +46,8 @@ def compat_packed(src: torch.Tensor, tgt: torch.Tensor, sigma_d: torch.Tensor) -
     src, tgt = _dev(src, "src"), _dev(tgt, "tgt")
     sigma_d = _dev(sigma_d.reshape(-1), "sigma_d")
     B, N, _ = src.shape
-    L = _lib.load()
-    nf = L.pdsc_compat_packed_floats(N)
-    Mp = torch.empty((B, nf), dtype=torch.float32, device=src.device)
-    check(L.pdsc_compat_packed_f32(_p(src), _p(tgt), B, N, _p(sigma_d), _p(Mp), _stream(src.device)),
-          "pdsc_compat_packed_f32")
+    Mp = torch.empty((B, query("pdsc_compat_packed_floats", N)), dtype=torch.float32, device=src.device)
+    call("pdsc_compat_packed_f32", src, tgt, B, N, sigma_d, Mp, device=src.device)
     T = 32
     nt = (N + T - 1) // T
     ti, tj = torch.triu_indices(nt, nt)
@@ -77,20 +62,19 @@ def compat_packed(src: torch.Tensor, tgt: torch.Tensor, sigma_d: torch.Tensor) -
 def pack_weights(cfg: _lib.PdscConfig, named: dict) -> torch.Tensor:
     """Pack reference state-dict tensors (on device) into the kernels' blob."""
     L = _lib.load()
-    n = L.pdsc_param_count(ctypes.byref(cfg))
+    n = L.pdsc_param_count(cfg)
     tensors, ptrs = [], (ctypes.c_void_p * n)()
     device = None
     for i in range(n):
-        key = L.pdsc_param_name(ctypes.byref(cfg), i).decode()
+        key = L.pdsc_param_name(cfg, i).decode()
         if key not in named:
             raise KeyError(f"missing parameter {key}")
         t = _dev(named[key].detach(), key)
         device = t.device
         tensors.append(t)
         ptrs[i] = t.data_ptr()
-    packed = torch.empty(L.pdsc_packed_weights_floats(ctypes.byref(cfg)), dtype=torch.float32,
-                         device=device)
-    check(L.pdsc_pack_weights(ctypes.byref(cfg), ptrs, _p(packed), _stream(device)), "pdsc_pack_weights")
+    packed = torch.empty(L.pdsc_packed_weights_floats(cfg), dtype=torch.float32, device=device)
+    call("pdsc_pack_weights", cfg, ptrs, packed, device=device)
     torch.cuda.current_stream(device).synchronize()  # keep `tensors` alive until the copies ran
     return packed
 
@@ -101,14 +85,11 @@ def encoder(cfg, packed, corr_pos, M, want_features=True):
     corr_pos, M = _dev(corr_pos, "corr_pos"), _dev(M, "M")
     B, N, _ = corr_pos.shape
     dev = corr_pos.device
-    L = _lib.load()
-    nb = L.pdsc_encoder_workspace_bytes(ctypes.byref(cfg), B, N)
-    ws = _workspace(nb, dev)
     feat = torch.empty((B, N, CH), dtype=torch.float32, device=dev) if want_features else None
     normed = torch.empty((B, N, CH), dtype=torch.float32, device=dev)
     conf = torch.empty((B, N), dtype=torch.float32, device=dev)
-    check(L.pdsc_encoder_f32(ctypes.byref(cfg), _p(packed), _p(corr_pos), _p(M), B, N, _p(feat),
-                             _p(normed), _p(conf), _p(ws), nb, _stream(dev)), "pdsc_encoder_f32")
+    call("pdsc_encoder_f32", cfg, packed, corr_pos, M, B, N, feat, normed, conf, device=dev,
+         ws=("pdsc_encoder_workspace_bytes", cfg, B, N))
     return feat, normed, conf
 
 
@@ -119,12 +100,9 @@ def attention(q, k, v, M, precision="h3"):
     if k.shape != q.shape or v.shape != q.shape or M.shape != (B, N, N):
         raise ValueError(f"q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} M {tuple(M.shape)}")
     pc = _lib.precision_code(precision)
-    L = _lib.load()
-    nb = L.pdsc_attention_workspace_bytes(B, N, C, pc)
-    ws = _workspace(nb, q.device)
     msg = torch.empty_like(q)
-    check(L.pdsc_attention_f32(_p(q), _p(k), _p(v), _p(M), B, N, C, pc, _p(msg), _p(ws), nb,
-                               _stream(q.device)), "pdsc_attention_f32")
+    call("pdsc_attention_f32", q, k, v, M, B, N, C, pc, msg, device=q.device,
+         ws=("pdsc_attention_workspace_bytes", B, N, C, pc))
     return msg
 
 
@@ -135,8 +113,7 @@ def pick_seeds(src, conf, radius: float, max_num: int):
     B, N = conf.shape
     seeds = torch.empty((B, max_num), dtype=torch.int32, device=src.device)
     lm = torch.empty((B, N), dtype=torch.float32, device=src.device)
-    check(_lib.load().pdsc_pick_seeds(_p(src), _p(conf), B, N, float(radius), int(max_num), _p(seeds),
-                                      _p(lm), _stream(src.device)), "pdsc_pick_seeds")
+    call("pdsc_pick_seeds", src, conf, B, N, float(radius), int(max_num), seeds, lm, device=src.device)
     return seeds, lm
 
 
@@ -146,13 +123,9 @@ def seed_knn(normed, seeds, k: int, precision="h3"):
     normed, seeds = _dev(normed, "normed"), _dev(seeds, "seeds", torch.int32)
     B, N, C = normed.shape
     S = seeds.shape[1]
-    L = _lib.load()
-    nb = L.pdsc_seed_knn_workspace_bytes(B, N, S)
-    ws = _workspace(nb, normed.device)
     out = torch.empty((B, S, k), dtype=torch.int32, device=normed.device)
-    check(L.pdsc_seed_knn(_p(normed), _p(seeds), B, N, C, S, int(k), _lib.precision_code(precision), _p(out),
-                          _p(ws), nb,
-                          _stream(normed.device)), "pdsc_seed_knn")
+    call("pdsc_seed_knn", normed, seeds, B, N, C, S, int(k), _lib.precision_code(precision), out,
+         device=normed.device, ws=("pdsc_seed_knn_workspace_bytes", B, N, S))
     return out
 
 
@@ -164,14 +137,11 @@ def nsm_weights(normed, src, tgt, knn, num_iterations, sigma, sigma_d, precision
     sigma, sigma_d = _dev(sigma.reshape(-1), "sigma"), _dev(sigma_d.reshape(-1), "sigma_d")
     B, N, C = normed.shape
     _, S, k = knn.shape
-    L = _lib.load()
-    nb = L.pdsc_nsm_workspace_bytes(B, N, S, k, int(num_iterations))
-    ws = _workspace(nb, normed.device)
     w = torch.empty((B, S, k), dtype=torch.float32, device=normed.device)
     it = torch.empty((B,), dtype=torch.int32, device=normed.device)
-    check(L.pdsc_nsm_weights(_p(normed), _p(src), _p(tgt), _p(knn), B, N, C, S, k, int(num_iterations),
-                             _lib.precision_code(precision), _p(sigma), _p(sigma_d), _p(w), _p(it), _p(ws), nb, _stream(normed.device)),
-          "pdsc_nsm_weights")
+    call("pdsc_nsm_weights", normed, src, tgt, knn, B, N, C, S, k, int(num_iterations),
+         _lib.precision_code(precision), sigma, sigma_d, w, it, device=normed.device,
+         ws=("pdsc_nsm_workspace_bytes", B, N, S, k, int(num_iterations)))
     return w, it
 
 
@@ -182,8 +152,7 @@ def rigid_transform_3d(A, B, weights=None):
     w = _dev(weights, "weights") if weights is not None else None
     nb, n, _ = A.shape
     out = torch.empty((nb, 4, 4), dtype=torch.float32, device=A.device)
-    check(_lib.load().pdsc_rigid_transform_3d(_p(A), _p(B), _p(w), nb, n, _p(out), _stream(A.device)),
-          "pdsc_rigid_transform_3d")
+    call("pdsc_rigid_transform_3d", A, B, w, nb, n, out, device=A.device)
     return out
 
 
@@ -200,12 +169,8 @@ def seed_hypotheses(src, tgt, knn, weights, tau: float):
     best = torch.empty((B,), dtype=torch.int32, device=dev)
     trans = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
     labels = torch.empty((B, N), dtype=torch.float32, device=dev)
-    L = _lib.load()
-    nb = L.pdsc_seed_hypotheses_workspace_bytes(B, S)
-    ws = _workspace(nb, dev)
-    check(L.pdsc_seed_hypotheses(_p(src), _p(tgt), _p(knn), _p(weights), B, N, S, k, float(tau),
-                                 _p(seed_trans), _p(fitness), _p(best), _p(trans), _p(labels), _p(ws), nb,
-                                 _stream(dev)), "pdsc_seed_hypotheses")
+    call("pdsc_seed_hypotheses", src, tgt, knn, weights, B, N, S, k, float(tau), seed_trans, fitness, best, trans,
+         labels, device=dev, ws=("pdsc_seed_hypotheses_workspace_bytes", B, S))
     return seed_trans, fitness, best, trans, labels
 
 
@@ -215,8 +180,7 @@ def post_refine(trans, src, tgt, thr: float):
     out = _dev(trans, "trans").clone()
     src, tgt = _dev(src, "src"), _dev(tgt, "tgt")
     B, N, _ = src.shape
-    check(_lib.load().pdsc_post_refine(_p(out), _p(src), _p(tgt), B, N, float(thr), _stream(src.device)),
-          "pdsc_post_refine")
+    call("pdsc_post_refine", out, src, tgt, B, N, float(thr), device=src.device)
     return out
 
 
@@ -240,9 +204,8 @@ class RangeError(RuntimeError):
 def range_flags(ws, B, device):
     """The forward's per-pair range marks from its workspace (pdsc_range_status;
     synchronises the device's current stream): a list of marked pair indices."""
-    L = _lib.load()
     flags = (ctypes.c_int32 * B)()
-    st = L.pdsc_range_status(_p(ws), B, flags, _stream(device))
+    st = _lib.load().pdsc_range_status(_p(ws), B, flags, _stream(device))
     if st not in (0, PDSC_ERR_RANGE):
         check(st, "pdsc_range_status")
     return [b for b in range(B) if flags[b]]
@@ -263,6 +226,37 @@ def _check_inputs(cfg, corr_pos, src, tgt):
                          f"src {tuple(src.shape)}, tgt {tuple(tgt.shape)} (expected [B,N,3])")
 
 
+def _forward_bytes(cfg, B, N, size_query="pdsc_forward_workspace_bytes"):
+    """The forward's workspace size for (cfg, B, N); 0 means unsupported: raises with pdsc_last_error."""
+    return query(size_query, cfg, B, N, required=True)
+
+
+def _forward_setup(cfg, corr_pos, src, tgt, size_query="pdsc_forward_workspace_bytes", ws=None):
+    """What every forward entry point starts with: the inputs as contiguous fp32
+    device tensors, their shape check and the workspace -- the caller-kept ``ws``
+    if it is large enough and on the inputs' device, else a fresh one.  Returns
+    (corr_pos, src, tgt, B, N, device, (workspace, its size query's bytes))."""
+    corr_pos, src, tgt = _dev(corr_pos, "corr_pos"), _dev(src, "src_keypts"), _dev(tgt, "tgt_keypts")
+    B, N, _ = src.shape
+    _check_inputs(cfg, corr_pos, src, tgt)
+    dev = src.device
+    nb = _forward_bytes(cfg, B, N, size_query)
+    if ws is None or ws.numel() < nb or ws.device != dev:
+        ws = _workspace(nb, dev)
+    return corr_pos, src, tgt, B, N, dev, (ws, nb)
+
+
+def _stage_outputs(cfg, B, N, dev):
+    """The five stage tensors of pdsc_forward_debug and the struct that points at them."""
+    S, k = int(N * cfg.ratio), min(cfg.k, N - 1)
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    st = {"conf": torch.empty((B, N), **f32), "seeds": torch.empty((B, S), **i32),
+          "knn": torch.empty((B, S, k), **i32), "weights": torch.empty((B, S, k), **f32),
+          "trans_pre_refine": torch.empty((B, 4, 4), **f32)}
+    return st, _lib.PdscForwardDebug(*(st[n].data_ptr() for n in ("conf", "seeds", "knn", "weights",
+                                                                   "trans_pre_refine")))
+
+
 def forward_testing(cfg, packed, corr_pos, src, tgt, debug=False, check_range=True, ws=None):
     """Full testing forward for B pairs: (final_trans [B,4,4], final_labels [B,N])
     (+ (confidence [B,N], seeds [B,S]) when ``debug``).  check_range: read the
@@ -271,27 +265,16 @@ def forward_testing(cfg, packed, corr_pos, src, tgt, debug=False, check_range=Tr
     the marks itself (``range_flags(ws, B, device)``) before trusting a pose.
     ws: a caller-kept uint8 device workspace of at least
     pdsc_forward_workspace_bytes (else one is allocated per call)."""
-    corr_pos, src, tgt = _dev(corr_pos, "corr_pos"), _dev(src, "src_keypts"), _dev(tgt, "tgt_keypts")
-    B, N, _ = src.shape
-    _check_inputs(cfg, corr_pos, src, tgt)
-    dev = src.device
-    L = _lib.load()
-    nb = L.pdsc_forward_workspace_bytes(ctypes.byref(cfg), B, N)
-    if nb == 0:
-        raise RuntimeError(f"unsupported configuration: {L.pdsc_last_error().decode()}")
-    if ws is None or ws.numel() < nb or ws.device != dev:
-        ws = _workspace(nb, dev)
+    corr_pos, src, tgt, B, N, dev, ws = _forward_setup(cfg, corr_pos, src, tgt, ws=ws)
     trans = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
     labels = torch.empty((B, N), dtype=torch.float32, device=dev)
     conf = seeds = None
     if debug:
         conf = torch.empty((B, N), dtype=torch.float32, device=dev)
         seeds = torch.empty((B, int(N * cfg.ratio)), dtype=torch.int32, device=dev)
-    check(L.pdsc_forward_testing(ctypes.byref(cfg), _p(packed), _p(corr_pos), _p(src), _p(tgt), B, N,
-                                 _p(trans), _p(labels), _p(conf), _p(seeds), _p(ws), nb, _stream(dev)),
-          "pdsc_forward_testing")
+    call("pdsc_forward_testing", cfg, packed, corr_pos, src, tgt, B, N, trans, labels, conf, seeds, device=dev, ws=ws)
     out = (trans, labels, conf, seeds) if debug else (trans, labels)
-    return _range_check(ws, B, dev, out) if check_range else out
+    return _range_check(ws[0], B, dev, out) if check_range else out
 
 
 def forward_stages(cfg, packed, corr_pos, src, tgt, check_range=True):
@@ -299,26 +282,13 @@ def forward_stages(cfg, packed, corr_pos, src, tgt, check_range=True):
     (pdsc_forward_testing_debug): dict of final_trans [B,4,4], final_labels
     [B,N], conf [B,N], seeds [B,S], knn [B,S,k], weights [B,S,k],
     trans_pre_refine [B,4,4] (int32 indices)."""
-    corr_pos, src, tgt = _dev(corr_pos, "corr_pos"), _dev(src, "src_keypts"), _dev(tgt, "tgt_keypts")
-    B, N, _ = src.shape
-    _check_inputs(cfg, corr_pos, src, tgt)
-    dev = src.device
-    L = _lib.load()
-    nb = L.pdsc_forward_workspace_bytes(ctypes.byref(cfg), B, N)
-    if nb == 0:
-        raise RuntimeError(f"unsupported configuration: {L.pdsc_last_error().decode()}")
-    ws = _workspace(nb, dev)
-    S, k = int(N * cfg.ratio), min(cfg.k, N - 1)
-    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-    out = {"final_trans": torch.empty((B, 4, 4), **f32), "final_labels": torch.empty((B, N), **f32),
-           "conf": torch.empty((B, N), **f32), "seeds": torch.empty((B, S), **i32),
-           "knn": torch.empty((B, S, k), **i32), "weights": torch.empty((B, S, k), **f32),
-           "trans_pre_refine": torch.empty((B, 4, 4), **f32)}
-    dbg = _lib.PdscForwardDebug(*(out[n].data_ptr() for n in ("conf", "seeds", "knn", "weights", "trans_pre_refine")))
-    check(L.pdsc_forward_testing_debug(ctypes.byref(cfg), _p(packed), _p(corr_pos), _p(src), _p(tgt), B, N,
-                                       _p(out["final_trans"]), _p(out["final_labels"]), ctypes.byref(dbg), _p(ws), nb,
-                                       _stream(dev)), "pdsc_forward_testing_debug")
-    return _range_check(ws, B, dev, out) if check_range else out
+    corr_pos, src, tgt, B, N, dev, ws = _forward_setup(cfg, corr_pos, src, tgt)
+    st, dbg = _stage_outputs(cfg, B, N, dev)
+    out = {"final_trans": torch.empty((B, 4, 4), dtype=torch.float32, device=dev),
+           "final_labels": torch.empty((B, N), dtype=torch.float32, device=dev), **st}
+    call("pdsc_forward_testing_debug", cfg, packed, corr_pos, src, tgt, B, N, out["final_trans"], out["final_labels"],
+         dbg, device=dev, ws=ws)
+    return _range_check(ws[0], B, dev, out) if check_range else out
 
 
 def forward_ragged(cfg, packed, corr_pos, src, tgt, counts, debug=False, check_range=True):
@@ -327,35 +297,17 @@ def forward_ragged(cfg, packed, corr_pos, src, tgt, counts, debug=False, check_r
     (final_trans [B,4,4], final_labels [B,N], rows past counts[b] zero); with
     ``debug``, also the dict of stage outputs (conf, seeds, knn, weights,
     trans_pre_refine) at the batch's strides."""
-    corr_pos, src, tgt = _dev(corr_pos, "corr_pos"), _dev(src, "src_keypts"), _dev(tgt, "tgt_keypts")
-    B, N, _ = src.shape
-    _check_inputs(cfg, corr_pos, src, tgt)
+    corr_pos, src, tgt, B, N, dev, ws = _forward_setup(cfg, corr_pos, src, tgt)
     counts = [int(c) for c in counts]
     if len(counts) != B:
         raise ValueError(f"{len(counts)} counts for {B} pairs")
-    dev = src.device
-    L = _lib.load()
-    nb = L.pdsc_forward_workspace_bytes(ctypes.byref(cfg), B, N)
-    if nb == 0:
-        raise RuntimeError(f"unsupported configuration: {L.pdsc_last_error().decode()}")
-    ws = _workspace(nb, dev)
     trans = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
     labels = torch.empty((B, N), dtype=torch.float32, device=dev)
-    cnt = (ctypes.c_int32 * B)(*counts)
-    dbg, st = None, None
-    if debug:
-        S, k = int(N * cfg.ratio), min(cfg.k, N - 1)
-        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-        st = {"conf": torch.empty((B, N), **f32), "seeds": torch.empty((B, S), **i32),
-              "knn": torch.empty((B, S, k), **i32), "weights": torch.empty((B, S, k), **f32),
-              "trans_pre_refine": torch.empty((B, 4, 4), **f32)}
-        dbg = _lib.PdscForwardDebug(*(st[n].data_ptr() for n in ("conf", "seeds", "knn", "weights",
-                                                                  "trans_pre_refine")))
-    check(L.pdsc_forward_testing_ragged(ctypes.byref(cfg), _p(packed), _p(corr_pos), _p(src), _p(tgt), B, N, cnt,
-                                        _p(trans), _p(labels), ctypes.byref(dbg) if dbg is not None else None, _p(ws),
-                                        nb, _stream(dev)), "pdsc_forward_testing_ragged")
+    st, dbg = _stage_outputs(cfg, B, N, dev) if debug else (None, None)
+    call("pdsc_forward_testing_ragged", cfg, packed, corr_pos, src, tgt, B, N, (ctypes.c_int32 * B)(*counts), trans,
+         labels, dbg, device=dev, ws=ws)
     out = (trans, labels, st) if debug else (trans, labels)
-    return _range_check(ws, B, dev, out) if check_range else out
+    return _range_check(ws[0], B, dev, out) if check_range else out
 
 
 def pad_pairs(tensors, N=None):
@@ -374,24 +326,15 @@ def forward_training(cfg, packed, corr_pos, src, tgt, want_M=True, want_seeds=Fa
     """Training-mode forward (models/PointDSC.py:158-163, :176, :182, :189-191) for
     B pairs: (final_trans [B,4,4], confidence [B,N], M [B,N,N] | None,
     seeds [B,S] | None).  Forward only: no gradients flow through the HIP path."""
-    corr_pos, src, tgt = _dev(corr_pos, "corr_pos"), _dev(src, "src_keypts"), _dev(tgt, "tgt_keypts")
-    B, N, _ = src.shape
-    _check_inputs(cfg, corr_pos, src, tgt)
-    dev = src.device
-    L = _lib.load()
-    nb = L.pdsc_forward_training_workspace_bytes(ctypes.byref(cfg), B, N)
-    if nb == 0:
-        raise RuntimeError(f"unsupported configuration: {L.pdsc_last_error().decode()}")
-    ws = _workspace(nb, dev)
+    corr_pos, src, tgt, B, N, dev, ws = _forward_setup(cfg, corr_pos, src, tgt,
+                                                       "pdsc_forward_training_workspace_bytes")
     trans = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
     conf = torch.empty((B, N), dtype=torch.float32, device=dev)
     M = torch.empty((B, N, N), dtype=torch.float32, device=dev) if want_M else None
     seeds = torch.empty((B, int(N * cfg.ratio)), dtype=torch.int32, device=dev) if want_seeds else None
-    check(L.pdsc_forward_training(ctypes.byref(cfg), _p(packed), _p(corr_pos), _p(src), _p(tgt), B, N,
-                                  _p(trans), _p(conf), _p(M), _p(seeds), _p(ws), nb, _stream(dev)),
-          "pdsc_forward_training")
+    call("pdsc_forward_training", cfg, packed, corr_pos, src, tgt, B, N, trans, conf, M, seeds, device=dev, ws=ws)
     out = (trans, conf, M, seeds)
-    return _range_check(ws, B, dev, out) if check_range else out
+    return _range_check(ws[0], B, dev, out) if check_range else out
 
 
 def spectral_matching_loss(M, gt_labels, balanced=True):
@@ -400,12 +343,9 @@ def spectral_matching_loss(M, gt_labels, balanced=True):
     if M.dim() != 3 or M.shape[1] != M.shape[2] or gt.shape != M.shape[:2]:
         raise ValueError(f"M {tuple(M.shape)} must be [B,N,N] and gt_labels {tuple(gt.shape)} [B,N]")
     B, N = gt.shape
-    L = _lib.load()
-    nb = L.pdsc_spectral_matching_loss_workspace_bytes(B, N)
-    ws = _workspace(nb, M.device)
     loss = torch.empty((), dtype=torch.float32, device=M.device)
-    check(L.pdsc_spectral_matching_loss(_p(M), _p(gt), B, N, int(bool(balanced)), _p(loss), _p(ws), nb,
-                                        _stream(M.device)), "pdsc_spectral_matching_loss")
+    call("pdsc_spectral_matching_loss", M, gt, B, N, int(bool(balanced)), loss, device=M.device,
+         ws=("pdsc_spectral_matching_loss_workspace_bytes", B, N))
     return loss
 
 
@@ -424,22 +364,29 @@ def consistency_graph(corr_pos, threshold: float, mode: str = "squared"):
     N, dev = corr_pos.shape[0], corr_pos.device
     adj = torch.empty((N, (N + 63) // 64), dtype=torch.int64, device=dev)
     degree = torch.empty(N, dtype=torch.int32, device=dev)
-    check(_lib.load().pdsc_consistency_graph(_p(corr_pos), N, float(threshold), _lib.EDGE_MODES[mode], _p(adj),
-                                             _p(degree), _stream(dev)), "pdsc_consistency_graph")
+    call("pdsc_consistency_graph", corr_pos, N, float(threshold), _lib.EDGE_MODES[mode], adj, degree, device=dev)
     return adj, degree
 
 
-class CliqueInfo:
-    """``pdsc_clique_result`` read back from the device (one synchronising copy)."""
-    __slots__ = ("size", "exact", "heuristic_size", "roots_incomplete", "nodes")
+class _Info:
+    """The fields ``__slots__`` names of the struct ``_struct``, read back from its
+    device tensor (one synchronising copy): ints for the C integers, floats for doubles."""
+    __slots__ = ()
+    _struct = None
 
     def __init__(self, result: torch.Tensor):
-        r = _lib.PdscCliqueResult.from_buffer_copy(result.cpu().numpy().tobytes())
-        self.size, self.exact, self.heuristic_size = int(r.size), int(r.exact), int(r.heuristic_size)
-        self.roots_incomplete, self.nodes = int(r.roots_incomplete), int(r.nodes)
+        r = read_struct(result, self._struct)
+        for k in self.__slots__:
+            setattr(self, k, getattr(r, k))
 
     def __repr__(self):
-        return "CliqueInfo(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+        return type(self).__name__ + "(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+
+
+class CliqueInfo(_Info):
+    """``pdsc_clique_result`` read back from the device (one synchronising copy)."""
+    __slots__ = ("size", "exact", "heuristic_size", "roots_incomplete", "nodes")
+    _struct = _lib.PdscCliqueResult
 
 
 def max_clique(adj, node_budget: int = 0, heuristic_only: bool = False):
@@ -454,18 +401,14 @@ def max_clique(adj, node_budget: int = 0, heuristic_only: bool = False):
     if adj.dim() != 2 or adj.shape[1] != (N + 63) // 64:
         raise ValueError(f"adj {tuple(adj.shape)} must be [N, ceil(N/64)]")
     dev = adj.device
-    L = _lib.load()
-    nb = L.pdsc_max_clique_workspace_bytes(N)
-    ws = _workspace(nb, dev)
+    ws = ("pdsc_max_clique_workspace_bytes", N)
     members = torch.empty(N, dtype=torch.int32, device=dev)
     labels = torch.empty(N, dtype=torch.float32, device=dev)
-    result = torch.empty(6, dtype=torch.int32, device=dev)
+    result = struct_buffer(_lib.PdscCliqueResult, dev).view(torch.int32)
     if heuristic_only:
-        check(L.pdsc_greedy_clique(_p(adj), N, _p(members), _p(result), _p(labels), _p(ws), nb, _stream(dev)),
-              "pdsc_greedy_clique")
+        call("pdsc_greedy_clique", adj, N, members, result, labels, device=dev, ws=ws)
     else:
-        check(L.pdsc_max_clique(_p(adj), N, int(node_budget), _p(members), _p(result), _p(labels), _p(ws), nb,
-                                _stream(dev)), "pdsc_max_clique")
+        call("pdsc_max_clique", adj, N, int(node_budget), members, result, labels, device=dev, ws=ws)
     return members, labels, result
 
 
@@ -473,30 +416,17 @@ def max_clique(adj, node_budget: int = 0, heuristic_only: bool = False):
 GNC_FACTOR, GNC_MAX_ITERATIONS, GNC_COST_THRESHOLD = 1.4, 10000, 1e-16  # TEASER_plus_plus.py:89-91
 
 
-class GncInfo:
+class GncInfo(_Info):
     """``pdsc_gnc_info`` read back from the device (one synchronising copy)."""
     __slots__ = ("iterations", "stop_reason", "cost", "mu")
-
-    def __init__(self, info: torch.Tensor):
-        r = _lib.PdscGncInfo.from_buffer_copy(info.cpu().numpy().tobytes())
-        self.iterations, self.stop_reason, self.cost, self.mu = int(r.iterations), int(r.stop_reason), r.cost, r.mu
-
-    def __repr__(self):
-        return "GncInfo(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+    _struct = _lib.PdscGncInfo
 
 
-class TeaserInfo:
+class TeaserInfo(_Info):
     """``pdsc_teaser_result`` read back from the device (one synchronising copy)."""
     __slots__ = ("valid", "clique_size", "clique_exact", "roots_incomplete", "gnc_iterations", "n_rotation_inliers",
                  "n_translation_inliers")
-
-    def __init__(self, result: torch.Tensor):
-        r = _lib.PdscTeaserResult.from_buffer_copy(result.cpu().numpy().tobytes())
-        for k in self.__slots__:
-            setattr(self, k, int(getattr(r, k)))
-
-    def __repr__(self):
-        return "TeaserInfo(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+    _struct = _lib.PdscTeaserResult
 
 
 def _tims(a, b, na, nb):
@@ -510,17 +440,16 @@ def gnc_tls_rotation(src_tims, dst_tims, noise_bound: float, gnc_factor: float =
                      max_iterations: int = GNC_MAX_ITERATIONS, cost_threshold: float = GNC_COST_THRESHOLD):
     """pdsc_gnc_tls_rotation (include/pdsc.h f9) on fp64 TIMs [K,3]: ``(R fp64
     [3,3], weights fp64 [K], inliers int32 [K], info)`` -- info the device copy of
-    ``pdsc_gnc_info`` (a uint8 [24] tensor; ``GncInfo(info)`` reads it and
+    ``pdsc_gnc_info`` (a uint8 tensor of its size; ``GncInfo(info)`` reads it and
     synchronises)."""
     a, b = _tims(src_tims, dst_tims, "src_tims", "dst_tims")
     K, dev = a.shape[0], a.device
     R = torch.empty((3, 3), dtype=torch.float64, device=dev)
     w = torch.empty(K, dtype=torch.float64, device=dev)
     inl = torch.empty(K, dtype=torch.int32, device=dev)
-    info = torch.empty(ctypes.sizeof(_lib.PdscGncInfo), dtype=torch.uint8, device=dev)
-    check(_lib.load().pdsc_gnc_tls_rotation(_p(a), _p(b), K, float(noise_bound), float(gnc_factor), int(max_iterations),
-                                            float(cost_threshold), _p(R), _p(w), _p(inl), _p(info), _stream(dev)),
-          "pdsc_gnc_tls_rotation")
+    info = struct_buffer(_lib.PdscGncInfo, dev)
+    call("pdsc_gnc_tls_rotation", a, b, K, float(noise_bound), float(gnc_factor), int(max_iterations),
+         float(cost_threshold), R, w, inl, info, device=dev)
     return R, w, inl, info
 
 
@@ -529,13 +458,10 @@ def tls_translation(src, dst, noise_bound: float):
     ``(t fp64 [3], inliers int32 [K])``."""
     a, b = _tims(src, dst, "src", "dst")
     K, dev = a.shape[0], a.device
-    L = _lib.load()
-    nb = L.pdsc_tls_translation_workspace_bytes(K)
-    ws = _workspace(nb, dev)
     t = torch.empty(3, dtype=torch.float64, device=dev)
     inl = torch.empty(K, dtype=torch.int32, device=dev)
-    check(L.pdsc_tls_translation(_p(a), _p(b), K, float(noise_bound), _p(t), _p(inl), _p(ws), nb, _stream(dev)),
-          "pdsc_tls_translation")
+    call("pdsc_tls_translation", a, b, K, float(noise_bound), t, inl, device=dev,
+         ws=("pdsc_tls_translation_workspace_bytes", K))
     return t, inl
 
 
@@ -543,22 +469,19 @@ def teaser_solve(src, tgt, noise_bound: float, node_budget: int = 0, gnc_factor:
                  max_iterations: int = GNC_MAX_ITERATIONS, cost_threshold: float = GNC_COST_THRESHOLD):
     """pdsc_teaser_solve on matched fp32 points src[i] <-> tgt[i] [N,3]: ``(trans
     fp64 [4,4], trans fp32 [4,4], labels fp32 [N], result)`` -- result the device
-    copy of ``pdsc_teaser_result`` (a uint8 [160] tensor whose first 128 bytes
-    are trans; ``TeaserInfo(result)`` reads the counters and synchronises)."""
+    copy of ``pdsc_teaser_result`` (a uint8 tensor of its size whose leading 16
+    doubles are trans; ``TeaserInfo(result)`` reads the counters and synchronises)."""
     src, tgt = _dev(src, "src"), _dev(tgt, "tgt")
     if src.dim() != 2 or src.shape[1] != 3 or src.shape != tgt.shape:
         raise ValueError(f"src {tuple(src.shape)} / tgt {tuple(tgt.shape)} must both be [N,3]")
     N, dev = src.shape[0], src.device
-    L = _lib.load()
-    nb = L.pdsc_teaser_solve_workspace_bytes(N)
-    ws = _workspace(nb, dev)
-    result = torch.empty(ctypes.sizeof(_lib.PdscTeaserResult), dtype=torch.uint8, device=dev)
+    result = struct_buffer(_lib.PdscTeaserResult, dev)
     t32 = torch.empty((4, 4), dtype=torch.float32, device=dev)
     labels = torch.empty(N, dtype=torch.float32, device=dev)
-    check(L.pdsc_teaser_solve(_p(src), _p(tgt), N, float(noise_bound), float(gnc_factor), int(max_iterations),
-                              float(cost_threshold), int(node_budget), _p(result), _p(t32), _p(labels), _p(ws), nb,
-                              _stream(dev)), "pdsc_teaser_solve")
-    return result[:128].view(torch.float64).view(4, 4), t32, labels, result
+    call("pdsc_teaser_solve", src, tgt, N, float(noise_bound), float(gnc_factor), int(max_iterations),
+         float(cost_threshold), int(node_budget), result, t32, labels, device=dev,
+         ws=("pdsc_teaser_solve_workspace_bytes", N))
+    return trans_view(result), t32, labels, result
 
 
 class ForwardPlan:
@@ -567,11 +490,8 @@ class ForwardPlan:
     Avoids the per-call allocator round trip in throughput loops (bench.py)."""
 
     def __init__(self, cfg, packed, B, N, device):
-        L = _lib.load()
         self.cfg, self.packed, self.B, self.N = cfg, packed, B, N
-        self.nb = L.pdsc_forward_workspace_bytes(ctypes.byref(cfg), B, N)
-        if self.nb == 0:
-            raise RuntimeError(f"unsupported configuration: {L.pdsc_last_error().decode()}")
+        self.nb = _forward_bytes(cfg, B, N)
         self.ws = _workspace(self.nb, device)
         self.trans = torch.empty((B, 4, 4), dtype=torch.float32, device=device)
         self.labels = torch.empty((B, N), dtype=torch.float32, device=device)
@@ -583,10 +503,8 @@ class ForwardPlan:
         _check_inputs(self.cfg, corr_pos, src, tgt)
         if tuple(src.shape[:2]) != (self.B, self.N):
             raise ValueError(f"plan is for B={self.B} N={self.N}, got {tuple(src.shape[:2])}")
-        s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream(src.device)
-        check(_lib.load().pdsc_forward_testing(
-            ctypes.byref(self.cfg), _p(self.packed), _p(corr_pos), _p(src), _p(tgt), self.B, self.N,
-            _p(self.trans), _p(self.labels), None, None, _p(self.ws), self.nb, s), "pdsc_forward_testing")
+        call("pdsc_forward_testing", self.cfg, self.packed, corr_pos, src, tgt, self.B, self.N, self.trans,
+             self.labels, None, None, device=src.device, ws=(self.ws, self.nb), stream=stream)
         return self.trans, self.labels
 
     def range_flags(self):

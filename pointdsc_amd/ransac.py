@@ -12,14 +12,13 @@ There is no CPU path: tensors must be HIP device tensors.
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 
 import torch
 
 from . import _lib
-from ._lib import check
-from .kernels import _dev, _p, _stream, _workspace
+from ._call import _p, call, read_struct, struct_buffer, trans_view
+from .kernels import _dev
 
 
 @dataclass
@@ -78,28 +77,22 @@ def registration_ransac_based_on_correspondence(source: torch.Tensor, target: to
         idx = corres.to(torch.int64)
         src, tgt = source[idx[:, 0]].contiguous(), target[idx[:, 1]].contiguous()
     n, H, ns = src.shape[0], int(max_iteration), int(ransac_n)
-    L = _lib.load()
-    nb = L.pdsc_ransac_workspace_bytes(n)
-    ws = _workspace(nb, dev)
-    res = torch.empty(20, dtype=torch.float64, device=dev)  # struct pdsc_ransac_result
+    res = struct_buffer(_lib.PdscRansacResult, dev)
     t32 = torch.empty((4, 4), dtype=torch.float32, device=dev)
     labels = torch.empty(n, dtype=torch.float32, device=dev)
-    dbg, dstruct = None, None
+    dbg = dstruct = None
     if debug and H >= 1 and ns in (3, 4):
         dbg = dict(samples=torch.zeros((H, ns), dtype=torch.int32, device=dev),
                    count=torch.zeros(H, dtype=torch.int32, device=dev),
                    sumsq=torch.zeros(H, dtype=torch.float64, device=dev),
                    trans=torch.zeros((H, 4, 4), dtype=torch.float64, device=dev))
-        dstruct = ctypes.byref(_lib.PdscRansacDebug(_p(dbg["samples"]), _p(dbg["count"]), _p(dbg["sumsq"]),
-                                                    _p(dbg["trans"])))
-    check(L.pdsc_ransac_correspondence(_p(src), _p(tgt), n, float(max_correspondence_distance), ns,
-                                       float(edge_similarity), H, float(confidence), int(seed) & (2 ** 64 - 1),
-                                       1 if refit else 0, _p(t32), _p(labels), _p(res), dstruct, _p(ws), nb,
-                                       _stream(dev)), "pdsc_ransac_correspondence")
-    tail = res[16:].cpu()
-    counts = tail[2:].view(torch.int32)
-    return RansacResult(res[:16].view(4, 4), t32, float(tail[0]), float(tail[1]), corres[labels > 0], labels,
-                        int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3]), dbg)
+        dstruct = _lib.PdscRansacDebug(*(_p(dbg[k]) for k in ("samples", "count", "sumsq", "trans")))
+    call("pdsc_ransac_correspondence", src, tgt, n, float(max_correspondence_distance), ns, float(edge_similarity), H,
+         float(confidence), int(seed) & (2 ** 64 - 1), 1 if refit else 0, t32, labels, res, dstruct, device=dev,
+         ws=("pdsc_ransac_workspace_bytes", n))
+    r = read_struct(res, _lib.PdscRansacResult)
+    return RansacResult(trans_view(res), t32, r.fitness, r.inlier_rmse, corres[labels > 0], labels, r.n_inliers,
+                        r.iterations, r.best, r.n_validated, dbg)
 
 
 def ransac_solver(src_keypts: torch.Tensor, tgt_keypts: torch.Tensor, pred_labels: torch.Tensor,

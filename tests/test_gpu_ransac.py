@@ -134,7 +134,7 @@ def test_early_stop(gpu_device):
 
 # ------------------------------------------------ 4. determinism and isolation
 def test_determinism_and_isolation(gpu_device, monkeypatch):
-    from pointdsc_amd import ransac as mod
+    from pointdsc_amd import _call as mod  # where the solver's workspace is allocated
     N, ratio, n, H, ds, ss = R.WHOLE_CASES["partial_round"]
     src, tgt, _, _ = R.make_case(ds, N, ratio)
     kw = dict(ransac_n=n, edge_similarity=0.9, max_iteration=H, seed=ss, debug=True)

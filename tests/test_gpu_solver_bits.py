@@ -26,6 +26,13 @@ fewer than three rows and with fewer than three inliers; GC-RANSAC with one
 cell holding every row at the sizes of its three cell paths (one wave up to 64
 rows, LDS up to 1024, global scratch above), a 4^6 grid, the local
 optimisation off and on.
+
+Every call with a result struct also records ``fields``: the scalars its Python
+wrapper hands out (the RansacResult / GcRansacResult / RegistrationResult
+dataclasses, CliqueInfo, GncInfo, TeaserInfo), floats as hex -- what the
+wrapper reads back from the struct must not move either.  The ICP, clique
+(exact and greedy), GNC-TLS rotation and TEASER calls are there for that: one
+call each on 64 rows.
 """
 import hashlib
 import json
@@ -73,11 +80,16 @@ def _bytes(t):
     return np.ascontiguousarray(t.detach().cpu().numpy()).tobytes()
 
 
-def _entry(outputs, struct):
-    """outputs: name -> device tensor; struct: the result struct's tensor (or None)."""
+def _entry(outputs, struct, fields=None):
+    """outputs: name -> device tensor; struct: the result struct's tensor (or None);
+    fields: the object whose int / float attributes the wrapper read from the struct."""
     e = {k: hashlib.sha256(_bytes(v)).hexdigest() for k, v in outputs.items()}
     if struct is not None:
         e["struct"] = _bytes(struct).hex()
+    if fields is not None:
+        names = getattr(fields, "__slots__", None) or list(vars(fields))
+        vals = {k: getattr(fields, k) for k in names}
+        e["fields"] = {k: v.hex() if type(v) is float else v for k, v in vals.items() if type(v) in (int, float)}
     return e
 
 
@@ -95,7 +107,8 @@ def run_ransac(dev, case):
     r = ransac(src, tgt, None, 0.1, ransac_n=ns, edge_similarity=es, max_iteration=H, confidence=conf, seed=7,
                refit=bool(refit), debug=True)
     debug = {"debug_" + k: v for k, v in r.debug.items()}
-    return _entry(dict(trans=r.transformation, trans_f32=r.transformation_f32, labels=r.labels, **debug), _struct(r))
+    return _entry(dict(trans=r.transformation, trans_f32=r.transformation_f32, labels=r.labels, **debug), _struct(r),
+                  r)
 
 
 def run_refit(dev, case):
@@ -119,10 +132,41 @@ def run_gc(dev, case):
     r = gc_ransac(src, tgt, 0.1, 0.975, max_iteration=H, confidence=conf, seed=7, local_optimization=bool(lo),
                   neighborhood_size=G, debug=True)
     debug = {"debug_" + k: v for k, v in r.debug.items()}
-    return _entry(dict(trans=r.transformation, trans_f32=r.transformation_f32, labels=r.labels, **debug), _struct(r))
+    return _entry(dict(trans=r.transformation, trans_f32=r.transformation_f32, labels=r.labels, **debug), _struct(r),
+                  r)
 
 
-GROUPS = {"ransac": (RANSAC_CASES, run_ransac), "refit": (REFIT_CASES, run_refit), "gc": (GC_CASES, run_gc)}
+# the calls whose result struct only the wrapper's read-back pins: 64 rows each
+INFO_CASES = [("icp",), ("clique", "exact"), ("clique", "greedy"), ("gnc",), ("teaser",)]
+
+
+def run_info(dev, case):
+    import torch
+    from pointdsc_amd import kernels as K
+    kind = case[0]
+    src, tgt, true, _ = R.make_case(4000 + len(kind), 64, 1.0 if kind == "icp" else 0.6)
+    s, t = torch.from_numpy(src).to(dev), torch.from_numpy(tgt).to(dev)
+    if kind == "icp":
+        from pointdsc_amd.icp import registration_icp
+        init = true.copy()
+        init[:3, 3] += 0.05
+        r = registration_icp(s, t, 0.2, torch.from_numpy(init).to(dev), want_correspondences=True)
+        return _entry(dict(trans=r.transformation, trans_f32=r.transformation_f32, correspondence=r.correspondence),
+                      None, r)
+    if kind == "clique":
+        adj, degree = K.consistency_graph(torch.cat([s, t], 1), 0.05, "length")
+        members, labels, result = K.max_clique(adj, heuristic_only=case[1] == "greedy")
+        return _entry(dict(adj=adj, degree=degree, members=members, labels=labels), result, K.CliqueInfo(result))
+    if kind == "gnc":
+        a, b = (s[1:] - s[:-1]).double(), (t[1:] - t[:-1]).double()
+        Rm, w, inl, info = K.gnc_tls_rotation(a, b, 0.05)
+        return _entry(dict(R=Rm, weights=w, inliers=inl), info, K.GncInfo(info))
+    trans, t32, labels, result = K.teaser_solve(s, t, 0.05)
+    return _entry(dict(trans=trans, trans_f32=t32, labels=labels), result, K.TeaserInfo(result))
+
+
+GROUPS = {"ransac": (RANSAC_CASES, run_ransac), "refit": (REFIT_CASES, run_refit), "gc": (GC_CASES, run_gc),
+          "info": (INFO_CASES, run_info)}
 
 
 def _key(group, case):

@@ -26,6 +26,179 @@ def test_library_exports_every_header_symbol():
     assert set(names) == set(_lib.EXPORTS)
 
 
+# ------------------------------------------------- include/pdsc.h against _lib.py
+P = ctypes.POINTER
+# C type -> ctypes.  Scalars (function parameters, return types and struct fields):
+SCALARS = {
+    "int32_t": ctypes.c_int32,
+    "int64_t": ctypes.c_int64,
+    "uint64_t": ctypes.c_uint64,
+    "size_t": ctypes.c_size_t,
+    "float": ctypes.c_float,
+    "double": ctypes.c_double,
+    "pdsc_stream_t": ctypes.c_void_p,
+}
+# Pointers: `const char *` -> c_char_p, `const pdsc_config *` -> CFG, a pointer to
+# pdsc_X_debug -> POINTER(PdscXDebug) or c_void_p, every other data pointer ->
+# c_void_p, but for the host pointers ctypes fills or reads in place:
+HOST_POINTERS = {
+    ("pdsc_pack_weights", "params_host_array"): P(ctypes.c_void_p),
+    ("pdsc_attention_layout", "Npad"): P(ctypes.c_int32),
+    ("pdsc_attention_layout", "nsplit"): P(ctypes.c_int32),
+    ("pdsc_encoder_plan", "fused"): P(ctypes.c_int32),
+    ("pdsc_encoder_plan_vfold", "vfold"): P(ctypes.c_int32),
+    ("pdsc_launch_plan", "out"): P(ctypes.c_int32),
+    ("pdsc_packed_block", "offsets"): P(ctypes.c_size_t),
+    ("pdsc_attention_timing", "start_events"): P(ctypes.c_void_p),
+    ("pdsc_attention_timing", "stop_events"): P(ctypes.c_void_p),
+    ("pdsc_attention_timing", "count"): P(ctypes.c_int32),
+    ("pdsc_forward_timing", "events"): P(ctypes.c_void_p),
+    ("pdsc_forward_timing", "count"): P(ctypes.c_int32),
+    ("pdsc_forward_testing_ragged", "counts"): P(ctypes.c_int32),
+    ("pdsc_ply_read_xyz", "n_points"): P(ctypes.c_int64),
+    ("pdsc_range_status", "flags"): P(ctypes.c_int32),
+}
+
+
+def _struct_class(c_name):
+    """pdsc_gc_ransac_result -> _lib.PdscGcRansacResult (None if _lib has no mirror)."""
+    return getattr(_lib, "".join(w.capitalize() for w in c_name.split("_")), None)
+
+
+def _declarator(text):
+    """'const float *const *tensors' / 'size_t offsets[5]' -> (base type, pointer depth, name, array length)."""
+    m = re.fullmatch(r"(.*?)(\w+)\s*(?:\[(\d+)\])?", text.strip(), re.S)
+    assert m, text
+    kind = m.group(1).replace("const", " ")
+    return " ".join(kind.replace("*", " ").split()), kind.count("*"), m.group(2), int(m.group(3)) if m.group(3) else None
+
+
+def parse_header():
+    """include/pdsc.h -> (structs {name: [(field, base, depth, array length)]},
+    functions {name: (return declarator, [parameter declarators])}).  Every
+    statement of the header is a typedef, an enum or a prototype: anything else
+    fails here, so no declaration is skipped silently."""
+    src = open(os.path.join(ROOT, "include", "pdsc.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    src = "\n".join(line for line in src.splitlines() if not line.lstrip().startswith("#"))
+    src = src.replace('extern "C" {', "")
+    structs = {}
+
+    def take_struct(m):
+        assert m.group(1) == m.group(3), m.group(0)
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(2).split(";"))):
+            first, *rest = decl.split(",")
+            base, depth, name, arr = _declarator(first)
+            fields.append((name, base, depth, arr))
+            for r in rest:  # `double fitness, inlier_rmse;`
+                _, d2, n2, a2 = _declarator("x " + r)
+                fields.append((n2, base, d2, a2))
+        structs[m.group(1)] = fields
+        return ""
+
+    src = re.sub(r"typedef\s+struct\s+(\w+)\s*\{([^}]*)\}\s*(\w+)\s*;", take_struct, src)
+    src = re.sub(r"enum\s+\w+\s*\{[^}]*\}\s*;", "", src)
+    src = re.sub(r"typedef\s+void\s*\*\s*pdsc_stream_t\s*;", "", src)
+    functions = {}
+    for stmt in filter(None, (s.strip() for s in src.split(";"))):
+        if stmt == "}":  # closes extern "C"
+            continue
+        m = re.fullmatch(r"(.*?\bpdsc_\w+)\s*\((.*)\)", stmt, re.S)
+        assert m, f"include/pdsc.h: not a prototype: {stmt!r}"
+        ret = _declarator(m.group(1))
+        params = [] if m.group(2).strip() == "void" else [_declarator(p) for p in m.group(2).split(",")]
+        assert ret[2] not in functions, ret[2]
+        functions[ret[2]] = (ret, params)
+    return structs, functions
+
+
+def _scalar_or_pointer(base, depth):
+    if depth == 0:
+        return SCALARS[base]
+    return ctypes.c_char_p if (base, depth) == ("char", 1) else ctypes.c_void_p
+
+
+def expected_parameter(fn, base, depth, name, arr):
+    """The ctypes types _PROTOS may give this parameter (see the table above)."""
+    if arr is not None:
+        depth += 1  # an array parameter is a pointer
+    if (fn, name) in HOST_POINTERS:
+        want = HOST_POINTERS[(fn, name)]
+        assert depth >= 1 and (base in ("void", "float") or want == P(SCALARS[base])), (fn, name, base)
+        return (want,)
+    if (base, depth) == ("pdsc_config", 1):
+        return (_lib.CFG,)
+    if depth == 1 and re.fullmatch(r"pdsc_\w+_debug", base):
+        return (P(_struct_class(base)), ctypes.c_void_p)
+    return (_scalar_or_pointer(base, depth),)
+
+
+def test_prototypes_match_header():
+    """_lib._PROTOS against include/pdsc.h: the return type and the ordered
+    parameter types of every function (only the names were compared before: a
+    swapped c_int32 / c_double loaded and ran).  Needs no library and no GPU."""
+    _, functions = parse_header()
+    assert sorted(functions) == header_functions() and set(functions) == set(_lib._PROTOS)
+    assert not [k for k in HOST_POINTERS if k[0] not in functions
+                or k[1] not in [p[2] for p in functions[k[0]][1]]], "HOST_POINTERS names a parameter the header lacks"
+    bad = []
+    for fn, ((rbase, rdepth, _, _), params) in functions.items():
+        res, args = _lib._PROTOS[fn]
+        if res != _scalar_or_pointer(rbase, rdepth):
+            bad.append(f"{fn}: returns {res.__name__}, the header says {rbase}{'*' * rdepth}")
+        if len(args) != len(params):
+            bad.append(f"{fn}: {len(args)} arguments, the header has {len(params)}")
+            continue
+        for i, (got, (base, depth, name, arr)) in enumerate(zip(args, params)):
+            if got not in expected_parameter(fn, base, depth, name, arr):
+                bad.append(f"{fn}: argument {i} ({name}) is {got.__name__}, the header says {base}{'*' * depth}")
+    assert not bad, "\n".join(bad)
+
+
+def test_workspace_functions_end_in_ws_bytes_stream():
+    """What _call.call relies on: a function that takes a workspace ends in (void
+    *workspace, size_t workspace_bytes, pdsc_stream_t stream), and every
+    *_workspace_bytes query has such a function."""
+    _, functions = parse_header()
+    users = {fn: p for fn, (_, p) in functions.items() if any(q[2] == "workspace" for q in p)}
+    for fn, p in users.items():
+        assert [(b, d) for b, d, _, _ in p[-3:]] == [("void", 1), ("size_t", 0), ("pdsc_stream_t", 0)], fn
+        assert [n for _, _, n, _ in p[-3:-1]] == ["workspace", "workspace_bytes"], fn
+    queries = [fn for fn in functions if fn.endswith("_workspace_bytes")]
+    assert len(queries) >= 20 and len(users) >= len(queries)
+    for q in queries:
+        stem = q[:-len("_workspace_bytes")]
+        assert any(fn.startswith(stem) for fn in users), q
+
+
+def test_structs_match_header():
+    """Every typedef struct of include/pdsc.h has a ctypes.Structure in _lib with
+    the same field names, order, types and array lengths, and the size and
+    offsets the C compiler gives the header's declaration (natural alignment)."""
+    structs, _ = parse_header()
+    assert len(structs) >= 12
+    for c_name, fields in structs.items():
+        cls = _struct_class(c_name)
+        assert cls is not None and issubclass(cls, ctypes.Structure), f"no ctypes mirror of {c_name}"
+        assert [f[0] for f in cls._fields_] == [f[0] for f in fields], c_name
+        offset = align = 0
+        for (name, got), (_, base, depth, arr) in zip(cls._fields_, fields):
+            want = _scalar_or_pointer(base, depth)
+            size = al = ctypes.sizeof(want)
+            if arr is not None:
+                want, size = want * arr, size * arr
+            assert got == want, f"{c_name}.{name} is {got.__name__}, the header says {base}{'*' * depth}[{arr}]"
+            offset = -(-offset // al) * al
+            assert getattr(cls, name).offset == offset, f"{c_name}.{name}"
+            offset, align = offset + size, max(align, al)
+        assert ctypes.sizeof(cls) == -(-offset // align) * align, c_name
+    sizes = {n: ctypes.sizeof(_struct_class(n)) for n in structs}
+    assert (sizes["pdsc_clique_result"], sizes["pdsc_gnc_info"], sizes["pdsc_icp_result"]) == (24, 24, 152)
+    assert sizes["pdsc_ransac_result"] == sizes["pdsc_gc_ransac_result"] == sizes["pdsc_teaser_result"] == 160
+
+
 def test_version():
     assert b"gfx950" in _lib.load().pdsc_version()
 

@@ -1,6 +1,7 @@
 """A/B timing of the batched testing forward (diagnostic): ms per forward for a
-few (B, N) shapes in THIS process (plan knobs such as PDSC_OVERLAP come from
-the environment; AB_SHAPES="8x5000,1x1000" picks the shapes).
+few (B, N) shapes in THIS process (plan knobs such as PDSC_FUSE or PDSC_W64
+come from the environment, read once per process by the library's launch plan;
+AB_SHAPES="8x5000,1x1000" picks the shapes).
 Usage: python tools/forward_ab.py [reps]"""
 import os
 import sys
