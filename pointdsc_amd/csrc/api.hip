@@ -1,4 +1,8 @@
-// api.hip -- the C ABI of libpdsc.so (declared in include/pdsc.h).
+// api.hip -- the forward: the testing and training forwards of include/pdsc.h,
+// the a-row stage entries that share their helpers (compat, encoder, attention,
+// seeds, seed kNN, NSM, rigid transform, hypotheses, refinement), weight
+// packing, and the plan, timing and diag queries.  Nothing else: every other
+// row's entry points live in the row's file (abi.hpp).
 //
 // Host-side orchestration only: argument checks, workspace carving and kernel
 // launches on the caller's stream.  No allocation, no synchronisation.
@@ -11,29 +15,19 @@
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "launch_plan.hpp"
 #include "pdsc_internal.hpp"
-#include "workspace.hpp"
 
 using namespace pdsc;
 
+namespace {
+thread_local std::string g_err;  // pdsc_last_error
+thread_local std::string g_name;
+}  // namespace
+
 namespace pdsc {
 thread_local int g_diag_qkv_delay = 0;  // pdsc_diag_qkv_delay (tests only)
-}
-
-namespace {
-
-thread_local std::string g_err;
-thread_local std::string g_name;
-
-// measurement hook (pdsc_attention_timing): events recorded around attention launches
-thread_local hipEvent_t *g_tstart = nullptr, *g_tstop = nullptr;
-thread_local int g_tcap = 0;
-thread_local int32_t *g_tcount = nullptr;
-// pdsc_forward_timing: PDSC_FORWARD_STAGES + 1 events per forward call
-thread_local hipEvent_t *g_fev = nullptr;
-thread_local int g_fcap = 0;
-thread_local int32_t *g_fcount = nullptr;
 
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -44,14 +38,18 @@ int fail(int code, const char *fmt, ...) {
     g_err = buf;
     return code;
 }
+}  // namespace pdsc
 
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(PDSC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+namespace {
 
-hipStream_t S_(pdsc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+// measurement hook (pdsc_attention_timing): events recorded around attention launches
+thread_local hipEvent_t *g_tstart = nullptr, *g_tstop = nullptr;
+thread_local int g_tcap = 0;
+thread_local int32_t *g_tcount = nullptr;
+// pdsc_forward_timing: PDSC_FORWARD_STAGES + 1 events per forward call
+thread_local hipEvent_t *g_fev = nullptr;
+thread_local int g_fcap = 0;
+thread_local int32_t *g_fcount = nullptr;
 
 int check_cfg(const pdsc_config *cfg) {
     if (!cfg) return fail(PDSC_ERR_ARG, "cfg is NULL");
@@ -378,30 +376,6 @@ FwdBufs carve_forward(Carve &c, const Dims &d) {
     return f;
 }
 
-int need_ws(size_t have, size_t need) {
-    if (have < need) return fail(PDSC_ERR_ARG, "workspace too small: %zu < %zu bytes", have, need);
-    return PDSC_OK;
-}
-
-}  // namespace
-
-#define RET_IF(x)                  \
-    do {                           \
-        int r_ = (x);              \
-        if (r_ != PDSC_OK) return r_; \
-    } while (0)
-
-namespace {
-int32_t check_nn_args(const float *a, const float *b, int32_t Ns, int32_t Nt, int32_t D, void *ws, size_t ws_bytes) {
-    if (!a || !b || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    if (Ns < 1 || Nt < 1 || D < 1 || D > 64) return fail(PDSC_ERR_ARG, "Ns=%d Nt=%d D=%d (1 <= D <= 64)", Ns, Nt, D);
-    return need_ws(ws_bytes, pdsc_mutual_nn_workspace_bytes(Ns, Nt));
-}
-
-__global__ void unpack_nn_kernel(const unsigned long long *key, int n, int32_t *out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (int32_t)(uint32_t)key[i];
-}
 }  // namespace
 
 extern "C" {
@@ -1079,552 +1053,6 @@ int32_t pdsc_range_poll(const void *ws, int32_t B, pdsc_stream_t stream) {
         if ((v >> 1) != seq) return fail(PDSC_ERR_HIP, "range word %u after the stream drained (expected %u)", v >> 1, seq);
     }
     if (v & 1u) return fail(PDSC_ERR_RANGE, "a pair of %d left the fp16 range (rerun it with PDSC_PRECISION_F32)", B);
-    return PDSC_OK;
-}
-
-static double *bind_sm_loss(Carve &c, int B, int N) { return c.take<double>(sm_loss_partial_doubles(B, N)); }
-
-size_t pdsc_spectral_matching_loss_workspace_bytes(int32_t B, int32_t N) {
-    if (B < 1 || N < 1) return 0;
-    Carve c(nullptr);
-    bind_sm_loss(c, B, N);
-    return c.off;
-}
-
-int32_t pdsc_spectral_matching_loss(const float *M, const float *gt_labels, int32_t B, int32_t N, int32_t balanced,
-                                    float *loss, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    if (!M || !gt_labels || !loss || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    if (B < 1 || N < 1) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    RET_IF(need_ws(ws_bytes, pdsc_spectral_matching_loss_workspace_bytes(B, N)));
-    Carve c(ws);
-    HIPCHK(launch_sm_loss(M, gt_labels, B, N, balanced, bind_sm_loss(c, B, N), loss, S_(stream)));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------------ f4 descriptor stage
-int32_t pdsc_ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t *n_points) {
-    if (!path || !n_points) return fail(PDSC_ERR_ARG, "null pointer");
-    std::string err;
-    if (ply_read_xyz(path, xyz, capacity, n_points, err) != 0) return fail(PDSC_ERR_ARG, "PLY: %s", err.c_str());
-    return PDSC_OK;
-}
-
-static int check_cloud(const float *pts, int32_t n, float r, int32_t max_nn) {
-    if (!pts) return fail(PDSC_ERR_ARG, "null points");
-    if (n < 1) return fail(PDSC_ERR_ARG, "n=%d", n);
-    if (!(r > 0.0f) || !std::isfinite(r)) return fail(PDSC_ERR_ARG, "radius / voxel size %g must be > 0", (double)r);
-    if (max_nn < 1 || max_nn > 128) return fail(PDSC_ERR_UNSUPPORTED, "max_nn=%d not in [1, 128]", max_nn);
-    return PDSC_OK;
-}
-
-// the device error flags of a grid pass, after the stream drained
-static int grid_status(const GridBufs &G, hipStream_t s) {
-    int e[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(e, G.err, sizeof e, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (e[0]) return fail(PDSC_ERR_ARG, "cloud extent / cell size >= 2^21 cells per axis");
-    if (e[1]) return fail(PDSC_ERR_UNSUPPORTED, "a radius neighbourhood holds > 1024 points within one d^2 bin");
-    return PDSC_OK;
-}
-
-size_t pdsc_radius_knn_workspace_bytes(int32_t n) { return n < 1 ? 0 : grid_workspace_bytes(n); }
-
-int32_t pdsc_radius_knn(const float *pts, int32_t n, float radius, int32_t max_nn, int32_t *nbr, double *dist2,
-                        int32_t *count, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_cloud(pts, n, radius, max_nn));
-    if (!nbr || !count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_radius_knn_workspace_bytes(n)));
-    hipStream_t s = S_(stream);
-    Carve c(ws);
-    GridBufs G;
-    bind_grid(c, n, G);
-    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
-    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, nbr, dist2, count, s));
-    return grid_status(G, s);
-}
-
-// the grid, then the neighbour lists [n][max_nn] and their lengths [n]
-struct NormalsBufs {
-    GridBufs grid;
-    int *nbr, *cnt;
-};
-static void bind_normals(Carve &c, int n, int max_nn, NormalsBufs &W) {
-    bind_grid(c, n, W.grid);
-    W.nbr = c.take<int>((size_t)n * max_nn);
-    W.cnt = c.take<int>((size_t)n);
-}
-
-size_t pdsc_estimate_normals_workspace_bytes(int32_t n, int32_t max_nn) {
-    if (n < 1 || max_nn < 1) return 0;
-    Carve c(nullptr);
-    NormalsBufs W;
-    bind_normals(c, n, max_nn, W);
-    return c.off;
-}
-
-int32_t pdsc_estimate_normals(const float *pts, int32_t n, float radius, int32_t max_nn, int32_t orient,
-                              const float *viewpoint, float *normals, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_cloud(pts, n, radius, max_nn));
-    if (!normals || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    if (orient != PDSC_NORMALS_OPEN3D && orient != PDSC_NORMALS_VIEWPOINT && orient != PDSC_NORMALS_CENTROID)
-        return fail(PDSC_ERR_ARG, "orient=%d (enum pdsc_normal_orientation)", orient);
-    if (orient == PDSC_NORMALS_VIEWPOINT && !viewpoint) return fail(PDSC_ERR_ARG, "PDSC_NORMALS_VIEWPOINT needs a viewpoint");
-    RET_IF(need_ws(ws_bytes, pdsc_estimate_normals_workspace_bytes(n, max_nn)));
-    hipStream_t s = S_(stream);
-    Carve c(ws);
-    NormalsBufs W;
-    bind_normals(c, n, max_nn, W);
-    const GridBufs &G = W.grid;
-    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
-    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, W.nbr, nullptr, W.cnt, s));
-    HIPCHK(launch_normals(pts, n, W.nbr, W.cnt, max_nn, G, orient, viewpoint, normals, s));
-    return grid_status(G, s);
-}
-
-size_t pdsc_voxel_down_sample_workspace_bytes(int32_t n) { return n < 1 ? 0 : grid_workspace_bytes(n); }
-
-int32_t pdsc_voxel_down_sample(const float *pts, const float *normals, int32_t n, float voxel_size, float *out_pts,
-                               float *out_normals, int32_t *out_count, void *ws, size_t ws_bytes,
-                               pdsc_stream_t stream) {
-    RET_IF(check_cloud(pts, n, voxel_size, 1));
-    if (!out_pts || !out_count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_voxel_down_sample_workspace_bytes(n)));
-    hipStream_t s = S_(stream);
-    Carve c(ws);
-    GridBufs G;
-    bind_grid(c, n, G);
-    HIPCHK(build_grid(pts, n, voxel_size, 0.5 * (double)voxel_size, G, s));
-    HIPCHK(launch_voxel_reduce(pts, normals, n, G, out_pts, out_normals, out_count, s));
-    return grid_status(G, s);
-}
-
-// the grid, then the neighbour lists and their d^2 [n][max_nn], the lengths [n] and the SPFH rows [n][33]
-struct FpfhBufs {
-    GridBufs grid;
-    int *nbr, *cnt;
-    double *d2, *spfh;
-};
-static void bind_fpfh(Carve &c, int n, int max_nn, FpfhBufs &W) {
-    bind_grid(c, n, W.grid);
-    W.nbr = c.take<int>((size_t)n * max_nn);
-    W.d2 = c.take<double>((size_t)n * max_nn);
-    W.cnt = c.take<int>((size_t)n);
-    W.spfh = c.take<double>((size_t)n * 33);
-}
-
-size_t pdsc_compute_fpfh_workspace_bytes(int32_t n, int32_t max_nn) {
-    if (n < 1 || max_nn < 1) return 0;
-    Carve c(nullptr);
-    FpfhBufs W;
-    bind_fpfh(c, n, max_nn, W);
-    return c.off;
-}
-
-int32_t pdsc_compute_fpfh(const float *pts, const float *normals, int32_t n, float radius, int32_t max_nn,
-                          double *fpfh, float *fpfh_normalized, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_cloud(pts, n, radius, max_nn));
-    if (!normals || !fpfh || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_compute_fpfh_workspace_bytes(n, max_nn)));
-    hipStream_t s = S_(stream);
-    Carve c(ws);
-    FpfhBufs W;
-    bind_fpfh(c, n, max_nn, W);
-    const GridBufs &G = W.grid;
-    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
-    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, W.nbr, W.d2, W.cnt, s));
-    HIPCHK(launch_fpfh(pts, normals, n, W.nbr, W.cnt, W.d2, max_nn, W.spfh, fpfh, fpfh_normalized, s));
-    return grid_status(G, s);
-}
-
-// ------------------------------------------------------- f5 ICP refinement
-size_t pdsc_icp_workspace_bytes(int32_t Ns, int32_t Nt) { return Ns < 1 || Nt < 1 ? 0 : icp_workspace_bytes(Ns, Nt); }
-
-// PDSC_ICP_ONE_WG=0: the launch-per-step path at every size (not in Knobs: read at every call, tests toggle it)
-static bool icp_one_wg() {
-    const char *e = getenv("PDSC_ICP_ONE_WG");
-    return !(e && e[0] == '0');
-}
-
-int32_t pdsc_icp_point_to_point(const float *source, int32_t Ns, const float *target, int32_t Nt,
-                                const double *init_trans, double max_distance, int32_t max_iteration,
-                                double relative_fitness, double relative_rmse, float *trans_f32,
-                                pdsc_icp_result *result, int32_t *corr, void *ws, size_t ws_bytes,
-                                pdsc_stream_t stream) {
-    if (Ns < 1 || Nt < 1) return fail(PDSC_ERR_ARG, "Ns=%d Nt=%d (need >= 1)", Ns, Nt);
-    if (!(max_distance > 0.0) || !std::isfinite(max_distance))
-        return fail(PDSC_ERR_ARG, "max_distance %g must be > 0 and finite", max_distance);
-    if (max_iteration < 0) return fail(PDSC_ERR_ARG, "max_iteration=%d", max_iteration);
-    if (!source || !target || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_icp_workspace_bytes(Ns, Nt)));
-    hipStream_t s = S_(stream);
-    GridBufs G;
-    HIPCHK(launch_icp(source, Ns, target, Nt, init_trans, max_distance, max_iteration, relative_fitness, relative_rmse,
-                      icp_one_wg(), trans_f32, result, corr, ws, G, s));
-    return grid_status(G, s);
-}
-
-// ------------------------------------------------ f6 RANSAC on correspondences
-int32_t pdsc_ransac_round(void) { return RANSAC_ROUND; }
-
-size_t pdsc_ransac_workspace_bytes(int32_t N) { return N < 1 ? 0 : ransac_workspace_bytes(N); }
-
-int32_t pdsc_ransac_correspondence(const float *src, const float *tgt, int32_t N, double max_distance,
-                                   int32_t ransac_n, double edge_similarity, int32_t max_iteration,
-                                   double confidence, uint64_t seed, int32_t refit, float *trans_f32, float *labels,
-                                   pdsc_ransac_result *result, const pdsc_ransac_debug *debug, void *ws,
-                                   size_t ws_bytes, pdsc_stream_t stream) {
-    if (ransac_n != 3 && ransac_n != 4)
-        return fail(PDSC_ERR_UNSUPPORTED, "ransac_n=%d: only 3 and 4 are implemented", ransac_n);
-    if (N < ransac_n) return fail(PDSC_ERR_ARG, "N=%d < ransac_n=%d", N, ransac_n);
-    if (max_iteration < 1) return fail(PDSC_ERR_ARG, "max_iteration=%d (need >= 1)", max_iteration);
-    if (!(max_distance > 0.0) || !std::isfinite(max_distance))
-        return fail(PDSC_ERR_ARG, "max_distance %g must be > 0 and finite", max_distance);
-    if (!(confidence > 0.0 && confidence <= 1.0)) return fail(PDSC_ERR_ARG, "confidence %g not in (0, 1]", confidence);
-    if (!(edge_similarity >= 0.0 && edge_similarity <= 1.0))
-        return fail(PDSC_ERR_ARG, "edge_similarity %g not in [0, 1]", edge_similarity);
-    if (!src || !tgt || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_ransac_workspace_bytes(N)));
-    HIPCHK(launch_ransac(src, tgt, N, max_distance, ransac_n, edge_similarity, max_iteration, confidence, seed,
-                         refit ? 1 : 0, trans_f32, labels, result, debug, ws, S_(stream)));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------ f7 filtered RANSAC front end
-size_t pdsc_nn2_workspace_bytes(int32_t N0, int32_t N1) { return N0 < 1 || N1 < 2 ? 0 : nn2_workspace_bytes(N0, N1); }
-
-static int32_t check_desc_args(int32_t N0, int32_t N1, int32_t D) {
-    if (N0 < 1 || N1 < 2 || D < 1) return fail(PDSC_ERR_ARG, "N0=%d N1=%d D=%d (need N0 >= 1, N1 >= 2, D >= 1)", N0, N1, D);
-    if (D > 64) return fail(PDSC_ERR_UNSUPPORTED, "D=%d > 64", D);
-    return PDSC_OK;
-}
-
-static int32_t nn2_call(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int split, int32_t *nn1,
-                        int32_t *nn2, int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_desc_args(N0, N1, D));
-    if (!f0 || !f1 || !nn1 || !nn2 || !rev || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_nn2_workspace_bytes(N0, N1)));
-    HIPCHK(launch_nn2(f0, f1, N0, N1, D, split, nn1, nn2, rev, ws, S_(stream)));
-    return PDSC_OK;
-}
-
-int32_t pdsc_nn2(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int32_t *nn1, int32_t *nn2,
-                 int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    return nn2_call(f0, f1, N0, N1, D, 0, nn1, nn2, rev, ws, ws_bytes, stream);
-}
-
-int32_t pdsc_nn2_split(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int32_t split,
-                       int32_t *nn1, int32_t *nn2, int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    if (split < 1) return fail(PDSC_ERR_ARG, "split=%d (need >= 1)", split);
-    return nn2_call(f0, f1, N0, N1, D, split, nn1, nn2, rev, ws, ws_bytes, stream);
-}
-
-int32_t pdsc_match_ratio(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, const int32_t *nn1,
-                         const int32_t *nn2, const int32_t *rev, int32_t *is_bb, float *feat_dist, float *norm,
-                         int32_t *num_bb, pdsc_stream_t stream) {
-    RET_IF(check_desc_args(N0, N1, D));
-    if (!f0 || !f1 || !nn1 || !nn2 || !feat_dist) return fail(PDSC_ERR_ARG, "null pointer");
-    if (rev && (!is_bb || !norm || !num_bb)) return fail(PDSC_ERR_ARG, "null pointer (is_bb, norm, num_bb go with rev)");
-    HIPCHK(launch_match_ratio(f0, f1, N0, N1, D, nn1, nn2, rev, is_bb, feat_dist, norm, num_bb, S_(stream)));
-    return PDSC_OK;
-}
-
-size_t pdsc_gpf_select_workspace_bytes(int32_t N0, int32_t grid_wid) {
-    return N0 < 1 || N0 > GPF_MAX_ROWS || grid_wid < 1 || grid_wid > 64 ? 0 : gpf_workspace_bytes(N0, grid_wid);
-}
-
-int32_t pdsc_gpf_select(const float *xyz0, const float *norm, const int32_t *num_bb, int32_t N0, int32_t grid_wid,
-                        double gpf_factor, int32_t *kept, int32_t *count, float *kept_norm,
-                        const pdsc_gpf_debug *debug, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    if (N0 < 1 || grid_wid < 1) return fail(PDSC_ERR_ARG, "N0=%d grid_wid=%d (need >= 1)", N0, grid_wid);
-    if (grid_wid > 64) return fail(PDSC_ERR_UNSUPPORTED, "grid_wid=%d > 64", grid_wid);
-    if (N0 > GPF_MAX_ROWS) return fail(PDSC_ERR_UNSUPPORTED, "N0=%d > %d (rank counting inside a cell)", N0, GPF_MAX_ROWS);
-    if (!(gpf_factor >= 0.0) || !std::isfinite(gpf_factor))
-        return fail(PDSC_ERR_ARG, "gpf_factor %g must be >= 0 and finite", gpf_factor);
-    if (!xyz0 || !norm || !num_bb || !kept || !count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_gpf_select_workspace_bytes(N0, grid_wid)));
-    HIPCHK(launch_gpf_select(xyz0, norm, num_bb, N0, grid_wid, gpf_factor, kept, count, kept_norm, debug, ws,
-                             S_(stream)));
-    return PDSC_OK;
-}
-
-int32_t pdsc_refit_inliers(const double *pose, const float *src, const float *tgt, int32_t N, double radius,
-                           double *trans, float *trans_f32, int32_t *count, float *labels, pdsc_stream_t stream) {
-    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
-    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(PDSC_ERR_ARG, "radius %g must be > 0 and finite", radius);
-    if (!pose || !src || !tgt || !trans) return fail(PDSC_ERR_ARG, "null pointer");
-    HIPCHK(launch_refit_inliers(pose, src, tgt, N, radius, trans, trans_f32, count, labels, S_(stream)));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------------------ f8 PMC baseline
-int32_t pdsc_consistency_graph(const float *corr_pos, int32_t N, double threshold, int32_t mode, uint64_t *adj,
-                               int32_t *degree, pdsc_stream_t stream) {
-    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
-    if (N > CLIQUE_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, CLIQUE_MAX_N);
-    if (!(threshold > 0.0) || !std::isfinite(threshold))
-        return fail(PDSC_ERR_ARG, "threshold %g must be > 0 and finite", threshold);
-    if (mode != PDSC_EDGE_SQUARED && mode != PDSC_EDGE_LENGTH)
-        return fail(PDSC_ERR_ARG, "mode=%d (PDSC_EDGE_SQUARED or PDSC_EDGE_LENGTH)", mode);
-    if (!corr_pos || !adj) return fail(PDSC_ERR_ARG, "null pointer");
-    HIPCHK(launch_consistency_graph(corr_pos, N, threshold, mode == PDSC_EDGE_LENGTH,
-                                    reinterpret_cast<unsigned long long *>(adj), degree, S_(stream)));
-    return PDSC_OK;
-}
-
-int32_t pdsc_max_clique_depth(void) { return clique_depth(); }
-int64_t pdsc_max_clique_default_budget(void) { return CLIQUE_DEFAULT_BUDGET; }
-
-size_t pdsc_max_clique_workspace_bytes(int32_t N) { return N < 1 || N > CLIQUE_MAX_N ? 0 : clique_workspace_bytes(N); }
-
-static int32_t clique_call(const uint64_t *adj, int32_t N, int64_t node_budget, bool exact, int32_t *members,
-                           pdsc_clique_result *result, float *labels, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
-    if (N > CLIQUE_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, CLIQUE_MAX_N);
-    if (node_budget < 0) return fail(PDSC_ERR_ARG, "node_budget=%lld (need >= 0; 0: the default)", (long long)node_budget);
-    if (!adj || !members || !result || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_max_clique_workspace_bytes(N)));
-    HIPCHK(launch_max_clique(reinterpret_cast<const unsigned long long *>(adj), N,
-                             node_budget ? (long long)node_budget : CLIQUE_DEFAULT_BUDGET, exact, members, result, labels,
-                             ws, S_(stream)));
-    return PDSC_OK;
-}
-
-int32_t pdsc_max_clique(const uint64_t *adj, int32_t N, int64_t node_budget, int32_t *members,
-                        pdsc_clique_result *result, float *labels, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    return clique_call(adj, N, node_budget, true, members, result, labels, ws, ws_bytes, stream);
-}
-
-int32_t pdsc_greedy_clique(const uint64_t *adj, int32_t N, int32_t *members, pdsc_clique_result *result, float *labels,
-                           void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    return clique_call(adj, N, 0, false, members, result, labels, ws, ws_bytes, stream);
-}
-
-// ---------------------------------------------------------------- f9 TEASER++
-static int32_t check_teaser_count(const char *what, int32_t n) {
-    if (n < 1) return fail(PDSC_ERR_ARG, "%s=%d (need >= 1)", what, n);
-    if (n > TEASER_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "%s=%d > %d", what, n, TEASER_MAX_N);
-    return PDSC_OK;
-}
-
-static int32_t check_noise_bound(double noise_bound) {
-    if (!(noise_bound > 0.0) || !std::isfinite(noise_bound))
-        return fail(PDSC_ERR_ARG, "noise_bound %g must be > 0 and finite", noise_bound);
-    return PDSC_OK;
-}
-
-static int32_t check_gnc(double gnc_factor, int32_t max_iterations, double cost_threshold) {
-    if (!(gnc_factor > 1.0) || !std::isfinite(gnc_factor))
-        return fail(PDSC_ERR_ARG, "gnc_factor %g must be > 1 and finite", gnc_factor);
-    if (max_iterations < 1) return fail(PDSC_ERR_ARG, "max_iterations=%d (need >= 1)", max_iterations);
-    if (cost_threshold != cost_threshold) return fail(PDSC_ERR_ARG, "cost_threshold is NaN");
-    return PDSC_OK;
-}
-
-int32_t pdsc_gnc_tls_rotation(const double *src_tims, const double *dst_tims, int32_t K, double noise_bound,
-                              double gnc_factor, int32_t max_iterations, double cost_threshold, double *R,
-                              double *weights, int32_t *inliers, pdsc_gnc_info *info, pdsc_stream_t stream) {
-    RET_IF(check_teaser_count("K", K));
-    RET_IF(check_noise_bound(noise_bound));
-    RET_IF(check_gnc(gnc_factor, max_iterations, cost_threshold));
-    if (!src_tims || !dst_tims || !R) return fail(PDSC_ERR_ARG, "null pointer");
-    HIPCHK(launch_gnc_rotation(src_tims, dst_tims, K, nullptr, noise_bound, gnc_factor, max_iterations, cost_threshold,
-                               R, weights, inliers, info, S_(stream)));
-    return PDSC_OK;
-}
-
-size_t pdsc_tls_translation_workspace_bytes(int32_t K) { return K < 1 || K > TEASER_MAX_N ? 0 : tls_workspace_bytes(K); }
-
-int32_t pdsc_tls_translation(const double *src, const double *dst, int32_t K, double noise_bound, double *t,
-                             int32_t *inliers, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_teaser_count("K", K));
-    RET_IF(check_noise_bound(noise_bound));
-    if (!src || !dst || !t || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_tls_translation_workspace_bytes(K)));
-    HIPCHK(launch_tls_translation(src, dst, K, nullptr, noise_bound, t, inliers, ws, S_(stream)));
-    return PDSC_OK;
-}
-
-size_t pdsc_teaser_solve_workspace_bytes(int32_t N) { return N < 1 || N > TEASER_MAX_N ? 0 : teaser_workspace_bytes(N); }
-
-int32_t pdsc_teaser_solve(const float *src, const float *tgt, int32_t N, double noise_bound, double gnc_factor,
-                          int32_t max_iterations, double cost_threshold, int64_t node_budget,
-                          pdsc_teaser_result *result, float *trans_f32, float *labels, void *ws, size_t ws_bytes,
-                          pdsc_stream_t stream) {
-    RET_IF(check_teaser_count("N", N));
-    RET_IF(check_noise_bound(noise_bound));
-    RET_IF(check_gnc(gnc_factor, max_iterations, cost_threshold));
-    if (node_budget < 0) return fail(PDSC_ERR_ARG, "node_budget=%lld (need >= 0; 0: the default)", (long long)node_budget);
-    if (!src || !tgt || !result || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_teaser_solve_workspace_bytes(N)));
-    HIPCHK(launch_teaser_solve(src, tgt, N, noise_bound, gnc_factor, max_iterations, cost_threshold,
-                               node_budget ? (long long)node_budget : CLIQUE_DEFAULT_BUDGET, result, trans_f32, labels,
-                               ws, S_(stream)));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------------------ f10 GC-RANSAC
-int32_t pdsc_gc_cell_bound(int32_t which) { return which == 0 ? GC_WAVE_CELL : which == 1 ? GC_LDS_CELL : 0; }
-
-int32_t pdsc_gc_ransac_round(void) { return RANSAC_ROUND; }
-
-static int32_t check_gc_rows(int32_t N, int32_t least) {
-    if (N < least) return fail(PDSC_ERR_ARG, "N=%d (need >= %d)", N, least);
-    if (N > GC_MAX_ROWS) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, GC_MAX_ROWS);
-    return PDSC_OK;
-}
-
-static int32_t check_gc_grid_size(int32_t G) {
-    if (G < 1 || G > GC_MAX_GRID) return fail(PDSC_ERR_ARG, "neighborhood_size G=%d not in [1, %d]", G, GC_MAX_GRID);
-    return PDSC_OK;
-}
-
-static int32_t check_gc_model(double threshold, double lambda) {
-    if (!(threshold > 0.0) || !std::isfinite(threshold))
-        return fail(PDSC_ERR_ARG, "threshold %g must be > 0 and finite", threshold);
-    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(PDSC_ERR_ARG, "spatial_coherence_weight %g not in [0, 1]", lambda);
-    return PDSC_OK;
-}
-
-size_t pdsc_gc_grid_workspace_bytes(int32_t N) { return N < 1 || N > GC_MAX_ROWS ? 0 : gc_grid_workspace_bytes(N); }
-
-int32_t pdsc_gc_grid(const float *src, const float *tgt, int32_t N, int32_t G, int32_t *order, int32_t *cell_start,
-                     int32_t *cell_of, int32_t *n_cells, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_gc_rows(N, 1));
-    RET_IF(check_gc_grid_size(G));
-    if (!src || !tgt || !order || !cell_start || !cell_of || !n_cells || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_gc_grid_workspace_bytes(N)));
-    HIPCHK(launch_gc_grid(src, tgt, N, G, order, cell_start, cell_of, n_cells, ws, S_(stream)));
-    return PDSC_OK;
-}
-
-size_t pdsc_gc_label_workspace_bytes(int32_t N) { return N < 1 || N > GC_MAX_ROWS ? 0 : gc_label_workspace_bytes(N); }
-
-int32_t pdsc_gc_label(const double *pose, const float *src, const float *tgt, int32_t N, const int32_t *order,
-                      const int32_t *cell_start, const int32_t *n_cells, double threshold, double lambda, float *labels,
-                      int32_t *count, const pdsc_gc_label_debug *debug, void *ws, size_t ws_bytes,
-                      pdsc_stream_t stream) {
-    RET_IF(check_gc_rows(N, 1));
-    RET_IF(check_gc_model(threshold, lambda));
-    if (!pose || !src || !tgt || !order || !cell_start || !n_cells || !labels || !count || !ws)
-        return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_gc_label_workspace_bytes(N)));
-    HIPCHK(launch_gc_label(pose, src, tgt, N, order, cell_start, n_cells, threshold, lambda, labels, count, debug, ws,
-                           S_(stream)));
-    return PDSC_OK;
-}
-
-size_t pdsc_gc_ransac_workspace_bytes(int32_t N) { return N < 3 || N > GC_MAX_ROWS ? 0 : gc_ransac_workspace_bytes(N); }
-
-int32_t pdsc_gc_ransac(const float *src, const float *tgt, int32_t N, double threshold, double lambda, int32_t G,
-                       int32_t max_iteration, double confidence, uint64_t seed, int32_t local_optimization,
-                       float *trans_f32, float *labels, pdsc_gc_ransac_result *result,
-                       const pdsc_gc_ransac_debug *debug, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_gc_rows(N, 3));
-    if (max_iteration < 1) return fail(PDSC_ERR_ARG, "max_iteration=%d (need >= 1)", max_iteration);
-    RET_IF(check_gc_model(threshold, lambda));
-    if (!(confidence > 0.0 && confidence <= 1.0)) return fail(PDSC_ERR_ARG, "confidence %g not in (0, 1]", confidence);
-    RET_IF(check_gc_grid_size(G));
-    if (!src || !tgt || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_gc_ransac_workspace_bytes(N)));
-    HIPCHK(launch_gc_ransac(src, tgt, N, threshold, lambda, G, max_iteration, confidence, seed,
-                            local_optimization ? 1 : 0, trans_f32, labels, result, debug, ws, S_(stream)));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------- f1 correspondence construction
-// the packed (distance, index) argmin keys of the rows [Ns] and the columns [Nt]
-struct NnKeys {
-    unsigned long long *rk, *ck;
-};
-static NnKeys bind_nn_keys(Carve &c, int Ns, int Nt) {
-    NnKeys k;
-    k.rk = c.take<unsigned long long>((size_t)Ns);
-    k.ck = c.take<unsigned long long>((size_t)Nt);
-    return k;
-}
-
-size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
-    Carve c(nullptr);
-    bind_nn_keys(c, Ns, Nt);
-    return c.off;
-}
-
-int32_t pdsc_mutual_nn(const float *src_desc, const float *tgt_desc, int32_t Ns, int32_t Nt, int32_t D,
-                       int32_t *nn_src, int32_t *nn_tgt, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_nn_args(src_desc, tgt_desc, Ns, Nt, D, ws, ws_bytes));
-    if (!nn_src || !nn_tgt) return fail(PDSC_ERR_ARG, "null pointer");
-    hipStream_t s = S_(stream);
-    Carve c(ws);
-    const NnKeys nk = bind_nn_keys(c, Ns, Nt);
-    unsigned long long *rk = nk.rk, *ck = nk.ck;
-    HIPCHK(launch_nn_argmin(src_desc, tgt_desc, Ns, Nt, D, rk, ck, s));
-    hipLaunchKernelGGL(unpack_nn_kernel, dim3((Ns + 255) / 256), dim3(256), 0, s, rk, Ns, nn_src);
-    hipLaunchKernelGGL(unpack_nn_kernel, dim3((Nt + 255) / 256), dim3(256), 0, s, ck, Nt, nn_tgt);
-    HIPCHK(hipGetLastError());
-    return PDSC_OK;
-}
-
-int32_t pdsc_build_correspondences(const float *src_desc, const float *tgt_desc, const float *src_xyz,
-                                   const float *tgt_xyz, int32_t Ns, int32_t Nt, int32_t D, int32_t mutual,
-                                   const double *gt_trans, double inlier_threshold, int32_t *corr,
-                                   int32_t *count, float *corr_pos, float *src_keypts, float *tgt_keypts,
-                                   float *labels, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_nn_args(src_desc, tgt_desc, Ns, Nt, D, ws, ws_bytes));
-    if (!src_xyz || !tgt_xyz || !corr || !count || !corr_pos || !src_keypts || !tgt_keypts)
-        return fail(PDSC_ERR_ARG, "null pointer");
-    if (gt_trans && !labels) return fail(PDSC_ERR_ARG, "gt_trans given without labels");
-    hipStream_t s = S_(stream);
-    Carve c(ws);
-    const NnKeys nk = bind_nn_keys(c, Ns, Nt);
-    unsigned long long *rk = nk.rk, *ck = nk.ck;
-    HIPCHK(launch_nn_argmin(src_desc, tgt_desc, Ns, Nt, D, rk, ck, s));
-    HIPCHK(launch_corr_build(rk, ck, src_xyz, tgt_xyz, Ns, mutual ? 1 : 0, gt_trans, inlier_threshold, corr, count,
-                             corr_pos, src_keypts, tgt_keypts, gt_trans ? labels : nullptr, s));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------ f3 spectral-matching baseline
-// M [N][N] and the power iteration's v, y, w [N]
-struct SmBufs {
-    float *M, *v, *y, *w;
-};
-static void bind_sm(Carve &c, int N, SmBufs &W) {
-    W.M = c.take<float>((size_t)N * N);
-    W.v = c.take<float>((size_t)N);
-    W.y = c.take<float>((size_t)N);
-    W.w = c.take<float>((size_t)N);
-}
-
-size_t pdsc_spectral_matching_workspace_bytes(int32_t N) {
-    Carve c(nullptr);
-    SmBufs W;
-    bind_sm(c, N, W);
-    return c.off;
-}
-
-int32_t pdsc_spectral_matching(const float *corr_pos, const float *src, const float *tgt, int32_t N,
-                               double inlier_threshold, double top_ratio, int32_t iters, float *trans,
-                               float *labels, float *leading_eig, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    if (!corr_pos || !src || !tgt || !trans || !labels || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    if (N < 1 || N > 46340 || iters < 0 || !(top_ratio >= 0.0 && top_ratio <= 1.0) || !(inlier_threshold > 0.0))
-        return fail(PDSC_ERR_ARG, "N=%d iters=%d top_ratio=%g inlier_threshold=%g", N, iters, top_ratio,
-                    inlier_threshold);
-    RET_IF(need_ws(ws_bytes, pdsc_spectral_matching_workspace_bytes(N)));
-    Carve c(ws);
-    SmBufs W;
-    bind_sm(c, N, W);
-    float *M = W.M, *v = leading_eig ? leading_eig : W.v, *y = W.y, *w = W.w;
-    const double sigma = inlier_threshold / 3.0;  // :34 (python float)
-    const float sig2 = (float)(sigma * sigma);    // tensor / python scalar -> fp32 divisor
-    const int S = (int)(N * top_ratio);           // int(leading_eig.shape[1] * top_ratio) (:46)
-    HIPCHK(launch_sm(corr_pos, src, tgt, N, sig2, S, iters, M, v, y, w, labels, trans, S_(stream)));
-    return PDSC_OK;
-}
-
-int32_t pdsc_sm_matvec(const float *M, const float *v, int32_t N, float *y, pdsc_stream_t stream) {
-    if (!M || !v || !y) return fail(PDSC_ERR_ARG, "null pointer");
-    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d", N);
-    HIPCHK(launch_sm_matvec(M, v, N, y, S_(stream)));
     return PDSC_OK;
 }
 

@@ -13,8 +13,10 @@
 // -ffp-contract=off, restated for this file below).  No floating-point atomics,
 // no integer atomics on global memory either: every output word has one writer,
 // so two calls are bitwise equal.  DESIGN.md §7 "PMC baseline" has the algorithm.
+#include <cmath>
+
+#include "abi.hpp"
 #include "pdsc_internal.hpp"
-#include "workspace.hpp"
 
 #pragma clang fp contract(off)
 
@@ -624,13 +626,6 @@ hipError_t launch_consistency_graph(const float *corr_pos, int N, double thr, bo
     return hipGetLastError();
 }
 
-int clique_depth() { return CLIQUE_DEPTH; }
-size_t clique_workspace_bytes(int N) {
-    Carve k(nullptr);
-    carve_clique(k, N);
-    return k.off;
-}
-
 void *reserve_clique(Carve &k, int N) {
     void *ws = k.take_bytes(0);  // where the next slice starts
     carve_clique(k, N);
@@ -643,4 +638,57 @@ hipError_t launch_max_clique(const u64 *adj, int N, long long budget, bool exact
                     : run_clique<1>(adj, N, budget, exact, members, res, labels, ws, s);
 }
 
+static int32_t clique_call(const uint64_t *adj, int32_t N, int64_t node_budget, bool exact, int32_t *members,
+                           pdsc_clique_result *result, float *labels, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
+    if (N > CLIQUE_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, CLIQUE_MAX_N);
+    if (node_budget < 0) return fail(PDSC_ERR_ARG, "node_budget=%lld (need >= 0; 0: the default)", (long long)node_budget);
+    if (!adj || !members || !result || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_max_clique_workspace_bytes(N)));
+    HIPCHK(launch_max_clique(reinterpret_cast<const u64 *>(adj), N,
+                             node_budget ? (long long)node_budget : CLIQUE_DEFAULT_BUDGET, exact, members, result, labels,
+                             ws, S_(stream)));
+    return PDSC_OK;
+}
+
 }  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+int32_t pdsc_consistency_graph(const float *corr_pos, int32_t N, double threshold, int32_t mode, uint64_t *adj,
+                               int32_t *degree, pdsc_stream_t stream) {
+    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
+    if (N > CLIQUE_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, CLIQUE_MAX_N);
+    if (!(threshold > 0.0) || !std::isfinite(threshold))
+        return fail(PDSC_ERR_ARG, "threshold %g must be > 0 and finite", threshold);
+    if (mode != PDSC_EDGE_SQUARED && mode != PDSC_EDGE_LENGTH)
+        return fail(PDSC_ERR_ARG, "mode=%d (PDSC_EDGE_SQUARED or PDSC_EDGE_LENGTH)", mode);
+    if (!corr_pos || !adj) return fail(PDSC_ERR_ARG, "null pointer");
+    HIPCHK(launch_consistency_graph(corr_pos, N, threshold, mode == PDSC_EDGE_LENGTH, reinterpret_cast<u64 *>(adj), degree,
+                                    S_(stream)));
+    return PDSC_OK;
+}
+
+int32_t pdsc_max_clique_depth(void) { return CLIQUE_DEPTH; }
+int64_t pdsc_max_clique_default_budget(void) { return CLIQUE_DEFAULT_BUDGET; }
+
+size_t pdsc_max_clique_workspace_bytes(int32_t N) {
+    if (N < 1 || N > CLIQUE_MAX_N) return 0;
+    Carve k(nullptr);
+    carve_clique(k, N);
+    return k.off;
+}
+
+int32_t pdsc_max_clique(const uint64_t *adj, int32_t N, int64_t node_budget, int32_t *members,
+                        pdsc_clique_result *result, float *labels, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    return clique_call(adj, N, node_budget, true, members, result, labels, ws, ws_bytes, stream);
+}
+
+int32_t pdsc_greedy_clique(const uint64_t *adj, int32_t N, int32_t *members, pdsc_clique_result *result, float *labels,
+                           void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    return clique_call(adj, N, 0, false, members, result, labels, ws, ws_bytes, stream);
+}
+
+}  // extern "C"

@@ -14,6 +14,7 @@
 //   corr_select    one workgroup: mutual test + ordered compaction (np.where order)
 //   corr_gather    one workgroup: keypoint gather, the reference's sequential
 //                  fp32 column mean, centring, ground-truth labels (fp64)
+#include "abi.hpp"
 #include "pdsc_internal.hpp"
 
 namespace pdsc {
@@ -80,9 +81,9 @@ __global__ __launch_bounds__(256) void nn_argmin_kernel(const float *__restrict_
     }
 }
 
-hipError_t launch_nn_argmin(const float *A, const float *B, int Na, int Nb, int D, unsigned long long *rowkey,
-                            unsigned long long *colkey, hipStream_t s) {
-    if (D < 1 || D > NN_DMAX) return hipErrorInvalidValue;
+// D in [1, NN_DMAX] (check_nn_args)
+static hipError_t launch_nn_argmin(const float *A, const float *B, int Na, int Nb, int D, unsigned long long *rowkey,
+                                   unsigned long long *colkey, hipStream_t s) {
     HIP_RET(hipMemsetAsync(rowkey, 0xff, (size_t)Na * sizeof(unsigned long long), s));
     HIP_RET(hipMemsetAsync(colkey, 0xff, (size_t)Nb * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(nn_argmin_kernel, dim3((Nb + NN_T - 1) / NN_T, (Na + NN_T - 1) / NN_T), dim3(256), 0, s, A,
@@ -171,15 +172,75 @@ __global__ __launch_bounds__(1024) void corr_gather_kernel(const float *__restri
     }
 }
 
-hipError_t launch_corr_build(const unsigned long long *rowkey, const unsigned long long *colkey,
-                             const float *src_xyz, const float *tgt_xyz, int Na, int mutual, const double *gt,
-                             double thr, int *corr, int *count, float *corr_pos, float *src_out, float *tgt_out,
-                             float *labels, hipStream_t s) {
-    hipLaunchKernelGGL(corr_select_kernel, dim3(1), dim3(1024), 0, s, rowkey, colkey, Na, mutual, corr, count);
-    HIP_RET(hipGetLastError());
-    hipLaunchKernelGGL(corr_gather_kernel, dim3(1), dim3(1024), 0, s, src_xyz, tgt_xyz, corr, count, gt, thr,
-                       corr_pos, src_out, tgt_out, labels);
-    return hipGetLastError();
+__global__ void unpack_nn_kernel(const unsigned long long *key, int n, int32_t *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (int32_t)(uint32_t)key[i];
+}
+
+// the packed (distance, index) argmin keys of the rows [Ns] and the columns [Nt]
+struct NnKeys {
+    unsigned long long *rk, *ck;
+};
+static NnKeys bind_nn_keys(Carve &c, int Ns, int Nt) {
+    NnKeys k;
+    k.rk = c.take<unsigned long long>((size_t)Ns);
+    k.ck = c.take<unsigned long long>((size_t)Nt);
+    return k;
+}
+
+static int32_t check_nn_args(const float *a, const float *b, int32_t Ns, int32_t Nt, int32_t D, void *ws,
+                             size_t ws_bytes) {
+    if (!a || !b || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    if (Ns < 1 || Nt < 1 || D < 1 || D > NN_DMAX)
+        return fail(PDSC_ERR_ARG, "Ns=%d Nt=%d D=%d (1 <= D <= 64)", Ns, Nt, D);
+    return need_ws(ws_bytes, pdsc_mutual_nn_workspace_bytes(Ns, Nt));
 }
 
 }  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+size_t pdsc_mutual_nn_workspace_bytes(int32_t Ns, int32_t Nt) {
+    Carve c(nullptr);
+    bind_nn_keys(c, Ns, Nt);
+    return c.off;
+}
+
+int32_t pdsc_mutual_nn(const float *src_desc, const float *tgt_desc, int32_t Ns, int32_t Nt, int32_t D,
+                       int32_t *nn_src, int32_t *nn_tgt, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_nn_args(src_desc, tgt_desc, Ns, Nt, D, ws, ws_bytes));
+    if (!nn_src || !nn_tgt) return fail(PDSC_ERR_ARG, "null pointer");
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    const NnKeys nk = bind_nn_keys(c, Ns, Nt);
+    HIPCHK(launch_nn_argmin(src_desc, tgt_desc, Ns, Nt, D, nk.rk, nk.ck, s));
+    hipLaunchKernelGGL(unpack_nn_kernel, dim3((Ns + 255) / 256), dim3(256), 0, s, nk.rk, Ns, nn_src);
+    hipLaunchKernelGGL(unpack_nn_kernel, dim3((Nt + 255) / 256), dim3(256), 0, s, nk.ck, Nt, nn_tgt);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
+}
+
+int32_t pdsc_build_correspondences(const float *src_desc, const float *tgt_desc, const float *src_xyz,
+                                   const float *tgt_xyz, int32_t Ns, int32_t Nt, int32_t D, int32_t mutual,
+                                   const double *gt_trans, double inlier_threshold, int32_t *corr,
+                                   int32_t *count, float *corr_pos, float *src_keypts, float *tgt_keypts,
+                                   float *labels, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_nn_args(src_desc, tgt_desc, Ns, Nt, D, ws, ws_bytes));
+    if (!src_xyz || !tgt_xyz || !corr || !count || !corr_pos || !src_keypts || !tgt_keypts)
+        return fail(PDSC_ERR_ARG, "null pointer");
+    if (gt_trans && !labels) return fail(PDSC_ERR_ARG, "gt_trans given without labels");
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    const NnKeys nk = bind_nn_keys(c, Ns, Nt);
+    HIPCHK(launch_nn_argmin(src_desc, tgt_desc, Ns, Nt, D, nk.rk, nk.ck, s));
+    hipLaunchKernelGGL(corr_select_kernel, dim3(1), dim3(1024), 0, s, nk.rk, nk.ck, Ns, mutual ? 1 : 0, corr, count);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(corr_gather_kernel, dim3(1), dim3(1024), 0, s, src_xyz, tgt_xyz, corr, count, gt_trans,
+                       inlier_threshold, corr_pos, src_keypts, tgt_keypts, gt_trans ? labels : nullptr);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
+}
+
+}  // extern "C"

@@ -34,9 +34,9 @@
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "pdsc_common.hpp"
 #include "pdsc_internal.hpp"
-#include "workspace.hpp"
 
 namespace pdsc {
 
@@ -603,31 +603,20 @@ hipError_t build_grid(const float *pts, int n, double cell, double half, const G
     return hipcub::DeviceScan::ExclusiveSum(tmp, tb, G.view.ucount, G.view.ustart, n, s);
 }
 
-hipError_t launch_radius_knn(const float *pts, int n, const GridBufs &G, double radius, int K, int *nbr, double *d2,
-                             int *cnt, hipStream_t s) {
+// the device error flags of a grid pass, after the stream drained
+int grid_status(const GridBufs &G, hipStream_t s) {
+    int e[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(e, G.err, sizeof e, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (e[0]) return fail(PDSC_ERR_ARG, "cloud extent / cell size >= 2^21 cells per axis");
+    if (e[1]) return fail(PDSC_ERR_UNSUPPORTED, "a radius neighbourhood holds > 1024 points within one d^2 bin");
+    return PDSC_OK;
+}
+
+static hipError_t launch_radius_knn(const float *pts, int n, const GridBufs &G, double radius, int K, int *nbr,
+                                    double *d2, int *cnt, hipStream_t s) {
     hipLaunchKernelGGL(radius_knn_kernel, dim3((n + KNN_WPB - 1) / KNN_WPB), dim3(KNN_WPB * 64), 0, s, pts, n, G.st,
                        radius, G.view, radius * radius, K, nbr, d2, cnt, G.err);
-    return hipGetLastError();
-}
-
-hipError_t launch_normals(const float *pts, int n, const int *nbr, const int *cnt, int K, const GridBufs &G,
-                          int orient, const float *viewpoint, float *nrm, hipStream_t s) {
-    hipLaunchKernelGGL(normals_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pts, n, nbr, cnt, K, G.st, orient,
-                       viewpoint, nrm);
-    return hipGetLastError();
-}
-
-hipError_t launch_voxel_reduce(const float *pts, const float *nrm, int n, const GridBufs &G, float *opts, float *onrm,
-                               int *count, hipStream_t s) {
-    hipLaunchKernelGGL(voxel_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pts, nrm, G.view, opts, onrm,
-                       count);
-    return hipGetLastError();
-}
-
-hipError_t launch_fpfh(const float *pts, const float *nrm, int n, const int *nbr, const int *cnt, const double *d2,
-                       int K, double *spfh, double *out, float *outn, hipStream_t s) {
-    hipLaunchKernelGGL(spfh_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pts, nrm, n, nbr, cnt, K, spfh);
-    hipLaunchKernelGGL(fpfh_kernel, dim3((n + 3) / 4), dim3(256), 0, s, n, nbr, cnt, d2, K, spfh, out, outn);
     return hipGetLastError();
 }
 
@@ -676,7 +665,7 @@ static double ply_value(const unsigned char *p, const std::string &t) {
     return v;
 }
 
-int ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t *n_out, std::string &err) {
+static int ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t *n_out, std::string &err) {
     FILE *f = fopen(path, "rb");
     if (!f) {
         err = std::string("cannot open ") + path;
@@ -815,4 +804,142 @@ int ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t *n_out,
     return 1;
 }
 
+// -------------------------------------------------------------- entry points
+static int check_cloud(const float *pts, int32_t n, float r, int32_t max_nn) {
+    if (!pts) return fail(PDSC_ERR_ARG, "null points");
+    if (n < 1) return fail(PDSC_ERR_ARG, "n=%d", n);
+    if (!(r > 0.0f) || !std::isfinite(r)) return fail(PDSC_ERR_ARG, "radius / voxel size %g must be > 0", (double)r);
+    if (max_nn < 1 || max_nn > 128) return fail(PDSC_ERR_UNSUPPORTED, "max_nn=%d not in [1, 128]", max_nn);
+    return PDSC_OK;
+}
+
+// the grid, then the neighbour lists [n][max_nn] and their lengths [n]
+struct NormalsBufs {
+    GridBufs grid;
+    int *nbr, *cnt;
+};
+static void bind_normals(Carve &c, int n, int max_nn, NormalsBufs &W) {
+    bind_grid(c, n, W.grid);
+    W.nbr = c.take<int>((size_t)n * max_nn);
+    W.cnt = c.take<int>((size_t)n);
+}
+
+// the grid, then the neighbour lists and their d^2 [n][max_nn], the lengths [n] and the SPFH rows [n][33]
+struct FpfhBufs {
+    GridBufs grid;
+    int *nbr, *cnt;
+    double *d2, *spfh;
+};
+static void bind_fpfh(Carve &c, int n, int max_nn, FpfhBufs &W) {
+    bind_grid(c, n, W.grid);
+    W.nbr = c.take<int>((size_t)n * max_nn);
+    W.d2 = c.take<double>((size_t)n * max_nn);
+    W.cnt = c.take<int>((size_t)n);
+    W.spfh = c.take<double>((size_t)n * 33);
+}
+
 }  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+int32_t pdsc_ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t *n_points) {
+    if (!path || !n_points) return fail(PDSC_ERR_ARG, "null pointer");
+    std::string err;
+    if (ply_read_xyz(path, xyz, capacity, n_points, err) != 0) return fail(PDSC_ERR_ARG, "PLY: %s", err.c_str());
+    return PDSC_OK;
+}
+
+size_t pdsc_radius_knn_workspace_bytes(int32_t n) { return n < 1 ? 0 : grid_workspace_bytes(n); }
+
+int32_t pdsc_radius_knn(const float *pts, int32_t n, float radius, int32_t max_nn, int32_t *nbr, double *dist2,
+                        int32_t *count, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_cloud(pts, n, radius, max_nn));
+    if (!nbr || !count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_radius_knn_workspace_bytes(n)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    GridBufs G;
+    bind_grid(c, n, G);
+    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
+    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, nbr, dist2, count, s));
+    return grid_status(G, s);
+}
+
+size_t pdsc_estimate_normals_workspace_bytes(int32_t n, int32_t max_nn) {
+    if (n < 1 || max_nn < 1) return 0;
+    Carve c(nullptr);
+    NormalsBufs W;
+    bind_normals(c, n, max_nn, W);
+    return c.off;
+}
+
+int32_t pdsc_estimate_normals(const float *pts, int32_t n, float radius, int32_t max_nn, int32_t orient,
+                              const float *viewpoint, float *normals, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_cloud(pts, n, radius, max_nn));
+    if (!normals || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    if (orient != PDSC_NORMALS_OPEN3D && orient != PDSC_NORMALS_VIEWPOINT && orient != PDSC_NORMALS_CENTROID)
+        return fail(PDSC_ERR_ARG, "orient=%d (enum pdsc_normal_orientation)", orient);
+    if (orient == PDSC_NORMALS_VIEWPOINT && !viewpoint) return fail(PDSC_ERR_ARG, "PDSC_NORMALS_VIEWPOINT needs a viewpoint");
+    RET_IF(need_ws(ws_bytes, pdsc_estimate_normals_workspace_bytes(n, max_nn)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    NormalsBufs W;
+    bind_normals(c, n, max_nn, W);
+    const GridBufs &G = W.grid;
+    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
+    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, W.nbr, nullptr, W.cnt, s));
+    hipLaunchKernelGGL(normals_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pts, n, W.nbr, W.cnt, max_nn, G.st, orient,
+                       viewpoint, normals);
+    HIPCHK(hipGetLastError());
+    return grid_status(G, s);
+}
+
+size_t pdsc_voxel_down_sample_workspace_bytes(int32_t n) { return n < 1 ? 0 : grid_workspace_bytes(n); }
+
+int32_t pdsc_voxel_down_sample(const float *pts, const float *normals, int32_t n, float voxel_size, float *out_pts,
+                               float *out_normals, int32_t *out_count, void *ws, size_t ws_bytes,
+                               pdsc_stream_t stream) {
+    RET_IF(check_cloud(pts, n, voxel_size, 1));
+    if (!out_pts || !out_count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_voxel_down_sample_workspace_bytes(n)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    GridBufs G;
+    bind_grid(c, n, G);
+    HIPCHK(build_grid(pts, n, voxel_size, 0.5 * (double)voxel_size, G, s));
+    hipLaunchKernelGGL(voxel_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pts, normals, G.view, out_pts,
+                       out_normals, out_count);
+    HIPCHK(hipGetLastError());
+    return grid_status(G, s);
+}
+
+size_t pdsc_compute_fpfh_workspace_bytes(int32_t n, int32_t max_nn) {
+    if (n < 1 || max_nn < 1) return 0;
+    Carve c(nullptr);
+    FpfhBufs W;
+    bind_fpfh(c, n, max_nn, W);
+    return c.off;
+}
+
+int32_t pdsc_compute_fpfh(const float *pts, const float *normals, int32_t n, float radius, int32_t max_nn,
+                          double *fpfh, float *fpfh_normalized, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_cloud(pts, n, radius, max_nn));
+    if (!normals || !fpfh || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_compute_fpfh_workspace_bytes(n, max_nn)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    FpfhBufs W;
+    bind_fpfh(c, n, max_nn, W);
+    const GridBufs &G = W.grid;
+    HIPCHK(build_grid(pts, n, radius, 0.0, G, s));
+    HIPCHK(launch_radius_knn(pts, n, G, radius, max_nn, W.nbr, W.d2, W.cnt, s));
+    hipLaunchKernelGGL(spfh_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pts, normals, n, W.nbr, W.cnt, max_nn, W.spfh);
+    hipLaunchKernelGGL(fpfh_kernel, dim3((n + 3) / 4), dim3(256), 0, s, n, W.nbr, W.cnt, W.d2, max_nn, W.spfh, fpfh,
+                       fpfh_normalized);
+    HIPCHK(hipGetLastError());
+    return grid_status(G, s);
+}
+
+}  // extern "C"

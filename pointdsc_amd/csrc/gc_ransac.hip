@@ -22,10 +22,16 @@
 //            at entry unless the round's best beat the so-far-best, and a fold
 //            kernel with the stop rule.  Nothing synchronises; integer atomics
 //            only: two calls are bitwise equal.
+#include <cmath>
+
 #include "ransac_shared.hpp"
 
 namespace pdsc {
 
+constexpr int GC_MAX_ROWS = 1 << 18;  // as pdsc_gpf_select's limit; also the LDS chunk rows of the one-pose scorer
+constexpr int GC_MAX_GRID = 1024;     // cells per axis: 6 axes of 10 bits in the 64-bit key
+constexpr int GC_WAVE_CELL = 64;      // cells up to this many rows: one wave, a row per lane
+constexpr int GC_LDS_CELL = 1024;     // up to this many: one workgroup in LDS; above: its global scratch
 constexpr int GC_GRID_WG = 1024;   // threads of the grid kernel
 constexpr int GC_GRID_LDS = 2048;  // rows up to which the grid's sort runs in LDS
 constexpr int GC_LABEL_WG = 256;   // threads of the label kernel
@@ -482,23 +488,11 @@ __global__ __launch_bounds__(RANSAC_FIN) void gc_finish_kernel(const float *__re
 // the grid kernel's scratch: the keys of the in-global-memory sort
 static u64 *bind_gc_grid(Carve &c, int N) { return c.take<u64>((size_t)N); }
 
-size_t gc_grid_workspace_bytes(int N) {
-    Carve c(nullptr);
-    bind_gc_grid(c, N);
-    return c.off;
-}
-
 static hipError_t gc_grid_enqueue(const float *src, const float *tgt, int N, int G, u64 *gkey, int *order,
                                   int *cell_start, int *cell_of, int *n_cells, hipStream_t s) {
     hipLaunchKernelGGL(gc_grid_kernel, dim3(1), dim3(GC_GRID_WG), 0, s, src, tgt, N, G, gkey, order, cell_start,
                        cell_of, n_cells);
     return hipGetLastError();
-}
-
-hipError_t launch_gc_grid(const float *src, const float *tgt, int N, int G, int *order, int *cell_start, int *cell_of,
-                          int *n_cells, void *ws, hipStream_t s) {
-    Carve c(ws);
-    return gc_grid_enqueue(src, tgt, N, G, bind_gc_grid(c, N), order, cell_start, cell_of, n_cells, s);
 }
 
 // the label kernel's scratch for cells above GC_LDS_CELL rows
@@ -508,32 +502,9 @@ static void bind_gc_label(Carve &c, int N, GcLabelArgs &A) {
     A.sP = c.take<double>((size_t)N);
 }
 
-size_t gc_label_workspace_bytes(int N) {
-    Carve c(nullptr);
-    GcLabelArgs A;
-    bind_gc_label(c, N, A);
-    return c.off;
-}
-
 static hipError_t gc_label_enqueue(const GcLabelArgs &A, int N, hipStream_t s) {
     hipLaunchKernelGGL(gc_label_kernel, dim3((N + GC_CELLS_PER_WG - 1) / GC_CELLS_PER_WG), dim3(GC_LABEL_WG), 0, s, A);
     return hipGetLastError();
-}
-
-hipError_t launch_gc_label(const double *pose, const float *src, const float *tgt, int N, const int *order,
-                           const int *cell_start, const int *n_cells, double threshold, double lambda, float *labels,
-                           int *count, const pdsc_gc_label_debug *debug, void *ws, hipStream_t s) {
-    GcLabelArgs A;
-    A.pose = pose, A.src = src, A.tgt = tgt, A.order = order, A.cell_start = cell_start, A.n_cells = n_cells;
-    A.den = 2.0 * (threshold * threshold), A.lambda = lambda;
-    A.labels = labels, A.count = count;
-    A.dbg = pdsc_gc_label_debug{nullptr, nullptr, nullptr, nullptr};
-    if (debug) A.dbg = *debug;
-    A.gate = nullptr, A.done = nullptr;
-    Carve c(ws);
-    bind_gc_label(c, N, A);
-    HIP_RET(hipMemsetAsync(count, 0, sizeof(int), s));
-    return gc_label_enqueue(A, N, s);
 }
 
 // The solver's workspace: the round buffers, its state, the grid (scratch and outputs) and the LO's labelling.
@@ -557,17 +528,106 @@ static void bind_gc_ransac(Carve &c, int N, GcBufs &W) {
     W.lab = c.take<float>((size_t)N);
 }
 
-size_t gc_ransac_workspace_bytes(int N) {
+static int32_t check_gc_rows(int32_t N, int32_t least) {
+    if (N < least) return fail(PDSC_ERR_ARG, "N=%d (need >= %d)", N, least);
+    if (N > GC_MAX_ROWS) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > %d", N, GC_MAX_ROWS);
+    return PDSC_OK;
+}
+
+static int32_t check_gc_grid_size(int32_t G) {
+    if (G < 1 || G > GC_MAX_GRID) return fail(PDSC_ERR_ARG, "neighborhood_size G=%d not in [1, %d]", G, GC_MAX_GRID);
+    return PDSC_OK;
+}
+
+static int32_t check_gc_model(double threshold, double lambda) {
+    if (!(threshold > 0.0) || !std::isfinite(threshold))
+        return fail(PDSC_ERR_ARG, "threshold %g must be > 0 and finite", threshold);
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(PDSC_ERR_ARG, "spatial_coherence_weight %g not in [0, 1]", lambda);
+    return PDSC_OK;
+}
+
+}  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+int32_t pdsc_gc_cell_bound(int32_t which) { return which == 0 ? GC_WAVE_CELL : which == 1 ? GC_LDS_CELL : 0; }
+
+int32_t pdsc_gc_ransac_round(void) { return RANSAC_ROUND; }
+
+size_t pdsc_gc_grid_workspace_bytes(int32_t N) {
+    if (N < 1 || N > GC_MAX_ROWS) return 0;
+    Carve c(nullptr);
+    bind_gc_grid(c, N);
+    return c.off;
+}
+
+int32_t pdsc_gc_grid(const float *src, const float *tgt, int32_t N, int32_t G, int32_t *order, int32_t *cell_start,
+                     int32_t *cell_of, int32_t *n_cells, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_gc_rows(N, 1));
+    RET_IF(check_gc_grid_size(G));
+    if (!src || !tgt || !order || !cell_start || !cell_of || !n_cells || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_gc_grid_workspace_bytes(N)));
+    Carve c(ws);
+    HIPCHK(gc_grid_enqueue(src, tgt, N, G, bind_gc_grid(c, N), order, cell_start, cell_of, n_cells, S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_gc_label_workspace_bytes(int32_t N) {
+    if (N < 1 || N > GC_MAX_ROWS) return 0;
+    Carve c(nullptr);
+    GcLabelArgs A;
+    bind_gc_label(c, N, A);
+    return c.off;
+}
+
+int32_t pdsc_gc_label(const double *pose, const float *src, const float *tgt, int32_t N, const int32_t *order,
+                      const int32_t *cell_start, const int32_t *n_cells, double threshold, double lambda, float *labels,
+                      int32_t *count, const pdsc_gc_label_debug *debug, void *ws, size_t ws_bytes,
+                      pdsc_stream_t stream) {
+    RET_IF(check_gc_rows(N, 1));
+    RET_IF(check_gc_model(threshold, lambda));
+    if (!pose || !src || !tgt || !order || !cell_start || !n_cells || !labels || !count || !ws)
+        return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_gc_label_workspace_bytes(N)));
+    hipStream_t s = S_(stream);
+    GcLabelArgs A;
+    A.pose = pose, A.src = src, A.tgt = tgt, A.order = order, A.cell_start = cell_start, A.n_cells = n_cells;
+    A.den = 2.0 * (threshold * threshold), A.lambda = lambda;
+    A.labels = labels, A.count = count;
+    A.dbg = pdsc_gc_label_debug{nullptr, nullptr, nullptr, nullptr};
+    if (debug) A.dbg = *debug;
+    A.gate = nullptr, A.done = nullptr;
+    Carve c(ws);
+    bind_gc_label(c, N, A);
+    HIPCHK(hipMemsetAsync(count, 0, sizeof(int), s));
+    HIPCHK(gc_label_enqueue(A, N, s));
+    return PDSC_OK;
+}
+
+size_t pdsc_gc_ransac_workspace_bytes(int32_t N) {
+    if (N < 3 || N > GC_MAX_ROWS) return 0;
     Carve c(nullptr);
     GcBufs W;
     bind_gc_ransac(c, N, W);
     return c.off;
 }
 
-hipError_t launch_gc_ransac(const float *src, const float *tgt, int N, double threshold, double lambda, int G, int H,
-                            double confidence, unsigned long long seed, int lo, float *trans_f32, float *labels,
-                            pdsc_gc_ransac_result *res, const pdsc_gc_ransac_debug *debug, void *ws, hipStream_t s) {
-    const int nchunks = (int)ransac_chunks(N);
+// Enqueues the grid (local_optimization != 0), every round with its LO steps and the finish.
+int32_t pdsc_gc_ransac(const float *src, const float *tgt, int32_t N, double threshold, double lambda, int32_t G,
+                       int32_t max_iteration, double confidence, uint64_t seed, int32_t local_optimization,
+                       float *trans_f32, float *labels, pdsc_gc_ransac_result *result,
+                       const pdsc_gc_ransac_debug *debug, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_gc_rows(N, 3));
+    if (max_iteration < 1) return fail(PDSC_ERR_ARG, "max_iteration=%d (need >= 1)", max_iteration);
+    RET_IF(check_gc_model(threshold, lambda));
+    if (!(confidence > 0.0 && confidence <= 1.0)) return fail(PDSC_ERR_ARG, "confidence %g not in (0, 1]", confidence);
+    RET_IF(check_gc_grid_size(G));
+    if (!src || !tgt || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_gc_ransac_workspace_bytes(N)));
+    hipStream_t s = S_(stream);
+    const int H = max_iteration, lo = local_optimization ? 1 : 0, nchunks = (int)ransac_chunks(N);
     Carve c(ws);
     GcBufs W;
     bind_gc_ransac(c, N, W);
@@ -580,7 +640,7 @@ hipError_t launch_gc_ransac(const float *src, const float *tgt, int N, double th
     const int init_blocks = dbg.count ? (int)(((size_t)H + 255) / 256) : 1;
     hipLaunchKernelGGL(gc_init_kernel, dim3(init_blocks), dim3(256), 0, s, st, B.st, H, dbg.count);
     if (lo) {
-        HIP_RET(gc_grid_enqueue(src, tgt, N, G, W.gkey, W.order, W.cell_start, W.cell_of, W.n_cells, s));
+        HIPCHK(gc_grid_enqueue(src, tgt, N, G, W.gkey, W.order, W.cell_start, W.cell_of, W.n_cells, s));
         A.pose = st->T, A.src = src, A.tgt = tgt, A.order = W.order, A.cell_start = W.cell_start, A.n_cells = W.n_cells;
         A.den = 2.0 * r2, A.lambda = lambda;
         A.labels = W.lab, A.count = &st->n_lab;
@@ -595,15 +655,16 @@ hipError_t launch_gc_ransac(const float *src, const float *tgt, int N, double th
                            q.nwg, r2, B);
         hipLaunchKernelGGL(gc_round_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, q.nwg, nchunks, r, H, lo, B, st, dbg);
         for (int step = 0; lo && step < GC_LO_STEPS; ++step) {
-            HIP_RET(gc_label_enqueue(A, N, s));
+            HIPCHK(gc_label_enqueue(A, N, s));
             hipLaunchKernelGGL(gc_lo_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, src, tgt, N, r2, W.lab, B.st, st);
         }
         hipLaunchKernelGGL(gc_fold_kernel, dim3(1), dim3(64), 0, s, N, r, confidence, B.st, st);
-        HIP_RET(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     hipLaunchKernelGGL(gc_finish_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, src, tgt, N, r2, st, lo ? W.n_cells : nullptr,
-                       trans_f32, labels, res);
-    return hipGetLastError();
+                       trans_f32, labels, result);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
 }
 
-}  // namespace pdsc
+}  // extern "C"

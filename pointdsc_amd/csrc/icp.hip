@@ -26,13 +26,18 @@
 // once the state's `done` word is set.  For Ns <= ICP_ONE_WG_MAX the whole loop
 // runs in one launch of one workgroup instead (the same two device
 // functions between __syncthreads, so the results are bitwise the same).
+#include <cmath>
+#include <cstdlib>
+
+#include "abi.hpp"
 #include "pdsc_common.hpp"
 #include "pdsc_internal.hpp"
-#include "workspace.hpp"
 
 namespace pdsc {
 
 typedef unsigned long long u64;
+constexpr int ICP_CHUNK = 256;       // source points per partial row (the fixed summation order)
+constexpr int ICP_ONE_WG_MAX = 512;  // Ns up to which the loop runs in one workgroup (the measured crossover)
 constexpr long long ICP_KEY_MAX = (1LL << GRID_KEY_BITS) - 1;
 constexpr int ICP_NSUM = 17;  // count, sum d^2, sum a [3], sum b [3], sum a b^T [9]
 
@@ -291,38 +296,61 @@ static void bind_icp(Carve &c, int Ns, int Nt, IcpBufs &I) {
     I.part = c.take<double>(icp_chunks(Ns) * ICP_NSUM);
 }
 
-size_t icp_workspace_bytes(int Ns, int Nt) {
+// PDSC_ICP_ONE_WG=0: the launch-per-step path at every size (not in Knobs: read at every call, tests toggle it)
+static bool icp_one_wg() {
+    const char *e = getenv("PDSC_ICP_ONE_WG");
+    return !(e && e[0] == '0');
+}
+
+}  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+size_t pdsc_icp_workspace_bytes(int32_t Ns, int32_t Nt) {
+    if (Ns < 1 || Nt < 1) return 0;
     Carve c(nullptr);
     IcpBufs I;
     bind_icp(c, Ns, Nt, I);
     return c.off;
 }
 
-hipError_t launch_icp(const float *src, int Ns, const float *tgt, int Nt, const double *init, double max_distance,
-                      int max_iter, double rel_fitness, double rel_rmse, bool one_wg, float *trans_f32,
-                      pdsc_icp_result *res, int *corr, void *ws, GridBufs &G, hipStream_t s) {
+// Builds the target's grid and enqueues the loop: one workgroup where
+// Ns <= ICP_ONE_WG_MAX (unless PDSC_ICP_ONE_WG=0), else a launch pair per step.
+int32_t pdsc_icp_point_to_point(const float *source, int32_t Ns, const float *target, int32_t Nt,
+                                const double *init_trans, double max_distance, int32_t max_iteration,
+                                double relative_fitness, double relative_rmse, float *trans_f32,
+                                pdsc_icp_result *result, int32_t *corr, void *ws, size_t ws_bytes,
+                                pdsc_stream_t stream) {
+    if (Ns < 1 || Nt < 1) return fail(PDSC_ERR_ARG, "Ns=%d Nt=%d (need >= 1)", Ns, Nt);
+    if (!(max_distance > 0.0) || !std::isfinite(max_distance))
+        return fail(PDSC_ERR_ARG, "max_distance %g must be > 0 and finite", max_distance);
+    if (max_iteration < 0) return fail(PDSC_ERR_ARG, "max_iteration=%d", max_iteration);
+    if (!source || !target || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_icp_workspace_bytes(Ns, Nt)));
+    hipStream_t s = S_(stream);
     Carve c(ws);
     IcpBufs I;
     bind_icp(c, Ns, Nt, I);
-    G = I.grid;
-    HIP_RET(build_grid(tgt, Nt, max_distance, 0.0, G, s));
-    IcpState *st = I.st;
-    double *part = I.part;
+    const GridBufs &G = I.grid;
+    HIPCHK(build_grid(target, Nt, max_distance, 0.0, G, s));
     const double r2 = max_distance * max_distance;
     const int nchunks = (int)icp_chunks(Ns);
-    if (one_wg && Ns <= ICP_ONE_WG_MAX) {
-        hipLaunchKernelGGL(icp_one_wg_kernel, dim3(1), dim3(ICP_WG), 0, s, src, Ns, tgt, G.st, max_distance, r2, G.view,
-                           init, max_iter, rel_fitness, rel_rmse, res, trans_f32, corr);
-        return hipGetLastError();
+    if (icp_one_wg() && Ns <= ICP_ONE_WG_MAX) {
+        hipLaunchKernelGGL(icp_one_wg_kernel, dim3(1), dim3(ICP_WG), 0, s, source, Ns, target, G.st, max_distance, r2,
+                           G.view, init_trans, max_iteration, relative_fitness, relative_rmse, result, trans_f32, corr);
+    } else {
+        hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(64), 0, s, I.st, init_trans);
+        for (int k = 0; k <= max_iteration; ++k) {
+            hipLaunchKernelGGL(icp_eval_kernel, dim3(nchunks), dim3(ICP_CHUNK), 0, s, source, Ns, target, G.st,
+                               max_distance, r2, G.view, I.st, nchunks, I.part, corr);
+            hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(64), 0, s, I.part, nchunks, Ns, G.st, I.st, k,
+                               max_iteration, relative_fitness, relative_rmse, result, trans_f32);
+        }
     }
-    hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(64), 0, s, st, init);
-    for (int k = 0; k <= max_iter; ++k) {
-        hipLaunchKernelGGL(icp_eval_kernel, dim3(nchunks), dim3(ICP_CHUNK), 0, s, src, Ns, tgt, G.st, max_distance, r2,
-                           G.view, st, nchunks, part, corr);
-        hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(64), 0, s, part, nchunks, Ns, G.st, st, k, max_iter,
-                           rel_fitness, rel_rmse, res, trans_f32);
-    }
-    return hipGetLastError();
+    HIPCHK(hipGetLastError());
+    return grid_status(G, s);
 }
 
-}  // namespace pdsc
+}  // extern "C"

@@ -27,8 +27,10 @@
 //                compaction in ascending row (the corr_select_kernel pattern).
 //
 // Integer atomics only: two calls are bitwise equal.
+#include <cmath>
+
+#include "abi.hpp"
 #include "pdsc_internal.hpp"
-#include "workspace.hpp"
 
 namespace pdsc {
 
@@ -36,6 +38,7 @@ typedef unsigned long long u64;
 constexpr int N2_T = 64;      // tile edge
 constexpr int N2_DMAX = 64;   // descriptor width limit (as pdsc_mutual_nn)
 constexpr u64 KEY_NONE = ~0ull;
+constexpr int NN2_MAX_SPLIT = 16;  // column splits per row stripe the workspace is sized for
 
 // Ordered pairs (k1 < k2 unless both are KEY_NONE) are updated by value with
 // min / max selects only: no branch, no store through a reference, so the
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(256) void nn2_merge_kernel(const u64 *__restrict__ 
     if (i < Nb) rev[i] = (int)(uint32_t)colkey[i];
 }
 
-int nn2_default_split(int Na, int Nb) {
+static int nn2_default_split(int Na, int Nb) {
     const int stripes = (Na + N2_T - 1) / N2_T, ntile = (Nb + N2_T - 1) / N2_T;
     int s = (1024 + stripes - 1) / stripes;  // four 35 KiB workgroups per CU on 256 CUs
     if (s > NN2_MAX_SPLIT) s = NN2_MAX_SPLIT;
@@ -175,32 +178,35 @@ static void bind_nn2(Carve &c, int Na, int Nb, Nn2Bufs &W) {
     W.colkey = c.take<u64>((size_t)Nb);
 }
 
-size_t nn2_workspace_bytes(int Na, int Nb) {
-    Carve c(nullptr);
-    Nn2Bufs W;
-    bind_nn2(c, Na, Nb, W);
-    return c.off;
+static int32_t check_desc_args(int32_t N0, int32_t N1, int32_t D) {
+    if (N0 < 1 || N1 < 2 || D < 1) return fail(PDSC_ERR_ARG, "N0=%d N1=%d D=%d (need N0 >= 1, N1 >= 2, D >= 1)", N0, N1, D);
+    if (D > N2_DMAX) return fail(PDSC_ERR_UNSUPPORTED, "D=%d > %d", D, N2_DMAX);
+    return PDSC_OK;
 }
 
-hipError_t launch_nn2(const float *A, const float *B, int Na, int Nb, int D, int split, int *nn1, int *nn2, int *rev,
-                      void *ws, hipStream_t s) {
-    if (D < 1 || D > N2_DMAX) return hipErrorInvalidValue;
-    const int ntile = (Nb + N2_T - 1) / N2_T;
-    int nsplit = split > 0 ? split : nn2_default_split(Na, Nb);
+// split: column splits per row stripe, 0 = nn2_default_split (clamped to the column tiles and NN2_MAX_SPLIT)
+static int32_t nn2_call(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int split, int32_t *nn1,
+                        int32_t *nn2, int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_desc_args(N0, N1, D));
+    if (!f0 || !f1 || !nn1 || !nn2 || !rev || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_nn2_workspace_bytes(N0, N1)));
+    hipStream_t s = S_(stream);
+    const int ntile = (N1 + N2_T - 1) / N2_T;
+    int nsplit = split > 0 ? split : nn2_default_split(N0, N1);
     if (nsplit > NN2_MAX_SPLIT) nsplit = NN2_MAX_SPLIT;
     if (nsplit > ntile) nsplit = ntile;
     Carve c(ws);
     Nn2Bufs W;
-    bind_nn2(c, Na, Nb, W);
-    u64 *rowpart = W.rowpart, *colkey = W.colkey;
-    HIP_RET(hipMemsetAsync(colkey, 0xff, (size_t)Nb * sizeof(u64), s));
-    hipLaunchKernelGGL(nn2_kernel, dim3(nsplit, (Na + N2_T - 1) / N2_T), dim3(256), 0, s, A, B, Na, Nb, D, nsplit,
-                       rowpart, colkey);
-    HIP_RET(hipGetLastError());
-    const int n = Na > Nb ? Na : Nb;
-    hipLaunchKernelGGL(nn2_merge_kernel, dim3((n + 255) / 256), dim3(256), 0, s, rowpart, colkey, Na, Nb, nsplit, nn1,
-                       nn2, rev);
-    return hipGetLastError();
+    bind_nn2(c, N0, N1, W);
+    HIPCHK(hipMemsetAsync(W.colkey, 0xff, (size_t)N1 * sizeof(u64), s));
+    hipLaunchKernelGGL(nn2_kernel, dim3(nsplit, (N0 + N2_T - 1) / N2_T), dim3(256), 0, s, f0, f1, N0, N1, D, nsplit,
+                       W.rowpart, W.colkey);
+    HIPCHK(hipGetLastError());
+    const int n = N0 > N1 ? N0 : N1;
+    hipLaunchKernelGGL(nn2_merge_kernel, dim3((n + 255) / 256), dim3(256), 0, s, W.rowpart, W.colkey, N0, N1, nsplit,
+                       nn1, nn2, rev);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
 }
 
 // ---------------------------------------------------------------- match_ratio
@@ -268,15 +274,6 @@ __global__ __launch_bounds__(1024) void ratio_norm_kernel(const float *__restric
         norm[i] = v;
     }
     if (tid == 0) num_bb[0] = cnt;
-}
-
-hipError_t launch_match_ratio(const float *f0, const float *f1, int N0, int N1, int D, const int *nn1, const int *nn2,
-                              const int *rev, int *is_bb, float *feat_dist, float *norm, int *num_bb, hipStream_t s) {
-    hipLaunchKernelGGL(ratio_rows_kernel, dim3((N0 + 255) / 256), dim3(256), 0, s, f0, f1, N0, N1, D, nn1, nn2, rev,
-                       is_bb, feat_dist);
-    HIP_RET(hipGetLastError());
-    if (rev) hipLaunchKernelGGL(ratio_norm_kernel, dim3(1), dim3(1024), 0, s, feat_dist, is_bb, N0, norm, num_bb);
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------ gpf
@@ -444,27 +441,82 @@ static void bind_gpf(Carve &c, int N0, int G, GpfBufs &B) {
     B.list = c.take<u64>((size_t)N0);
 }
 
-size_t gpf_workspace_bytes(int N0, int G) {
+// Rows pdsc_gpf_select accepts: a truncated cell of n rows costs n^2 word compares (gpf_rank_kernel), so one
+// cell holding every row costs N0^2 -- 6.9e10 at this limit, well under a second on 256 CUs.
+constexpr int GPF_MAX_ROWS = 1 << 18;
+
+}  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+size_t pdsc_nn2_workspace_bytes(int32_t N0, int32_t N1) {
+    if (N0 < 1 || N1 < 2) return 0;
     Carve c(nullptr);
-    GpfBufs B;
-    bind_gpf(c, N0, G, B);
+    Nn2Bufs W;
+    bind_nn2(c, N0, N1, W);
     return c.off;
 }
 
-hipError_t launch_gpf_select(const float *xyz0, const float *norm, const int *num_bb, int N0, int G, double factor,
-                             int *kept, int *count, float *kept_norm, const pdsc_gpf_debug *debug, void *ws,
-                             hipStream_t s) {
-    Carve c(ws);
-    GpfBufs B;
-    bind_gpf(c, N0, G, B);
-    pdsc_gpf_debug dbg = {nullptr, nullptr, nullptr, nullptr};
-    if (debug) dbg = *debug;
-    hipLaunchKernelGGL(gpf_cells_kernel, dim3(1), dim3(1024), 0, s, xyz0, N0, G, num_bb, factor, B, dbg);
-    hipLaunchKernelGGL(gpf_scatter_kernel, dim3((N0 + 255) / 256), dim3(256), 0, s, norm, N0, B);
-    hipLaunchKernelGGL(gpf_rank_kernel, dim3((N0 + 255) / 256), dim3(256), 0, s, norm, N0, B);
-    HIP_RET(hipGetLastError());
-    hipLaunchKernelGGL(gpf_compact_kernel, dim3(1), dim3(1024), 0, s, B.keep, norm, N0, kept, count, kept_norm);
-    return hipGetLastError();
+int32_t pdsc_nn2(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int32_t *nn1, int32_t *nn2,
+                 int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    return nn2_call(f0, f1, N0, N1, D, 0, nn1, nn2, rev, ws, ws_bytes, stream);
 }
 
-}  // namespace pdsc
+int32_t pdsc_nn2_split(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, int32_t split,
+                       int32_t *nn1, int32_t *nn2, int32_t *rev, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    if (split < 1) return fail(PDSC_ERR_ARG, "split=%d (need >= 1)", split);
+    return nn2_call(f0, f1, N0, N1, D, split, nn1, nn2, rev, ws, ws_bytes, stream);
+}
+
+// rev == nullptr: only feat_dist
+int32_t pdsc_match_ratio(const float *f0, const float *f1, int32_t N0, int32_t N1, int32_t D, const int32_t *nn1,
+                         const int32_t *nn2, const int32_t *rev, int32_t *is_bb, float *feat_dist, float *norm,
+                         int32_t *num_bb, pdsc_stream_t stream) {
+    RET_IF(check_desc_args(N0, N1, D));
+    if (!f0 || !f1 || !nn1 || !nn2 || !feat_dist) return fail(PDSC_ERR_ARG, "null pointer");
+    if (rev && (!is_bb || !norm || !num_bb)) return fail(PDSC_ERR_ARG, "null pointer (is_bb, norm, num_bb go with rev)");
+    hipStream_t s = S_(stream);
+    hipLaunchKernelGGL(ratio_rows_kernel, dim3((N0 + 255) / 256), dim3(256), 0, s, f0, f1, N0, N1, D, nn1, nn2, rev,
+                       is_bb, feat_dist);
+    HIPCHK(hipGetLastError());
+    if (rev) hipLaunchKernelGGL(ratio_norm_kernel, dim3(1), dim3(1024), 0, s, feat_dist, is_bb, N0, norm, num_bb);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
+}
+
+size_t pdsc_gpf_select_workspace_bytes(int32_t N0, int32_t grid_wid) {
+    if (N0 < 1 || N0 > GPF_MAX_ROWS || grid_wid < 1 || grid_wid > 64) return 0;
+    Carve c(nullptr);
+    GpfBufs B;
+    bind_gpf(c, N0, grid_wid, B);
+    return c.off;
+}
+
+int32_t pdsc_gpf_select(const float *xyz0, const float *norm, const int32_t *num_bb, int32_t N0, int32_t grid_wid,
+                        double gpf_factor, int32_t *kept, int32_t *count, float *kept_norm,
+                        const pdsc_gpf_debug *debug, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    if (N0 < 1 || grid_wid < 1) return fail(PDSC_ERR_ARG, "N0=%d grid_wid=%d (need >= 1)", N0, grid_wid);
+    if (grid_wid > 64) return fail(PDSC_ERR_UNSUPPORTED, "grid_wid=%d > 64", grid_wid);
+    if (N0 > GPF_MAX_ROWS) return fail(PDSC_ERR_UNSUPPORTED, "N0=%d > %d (rank counting inside a cell)", N0, GPF_MAX_ROWS);
+    if (!(gpf_factor >= 0.0) || !std::isfinite(gpf_factor))
+        return fail(PDSC_ERR_ARG, "gpf_factor %g must be >= 0 and finite", gpf_factor);
+    if (!xyz0 || !norm || !num_bb || !kept || !count || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_gpf_select_workspace_bytes(N0, grid_wid)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    GpfBufs B;
+    bind_gpf(c, N0, grid_wid, B);
+    pdsc_gpf_debug dbg = {nullptr, nullptr, nullptr, nullptr};
+    if (debug) dbg = *debug;
+    hipLaunchKernelGGL(gpf_cells_kernel, dim3(1), dim3(1024), 0, s, xyz0, N0, grid_wid, num_bb, gpf_factor, B, dbg);
+    hipLaunchKernelGGL(gpf_scatter_kernel, dim3((N0 + 255) / 256), dim3(256), 0, s, norm, N0, B);
+    hipLaunchKernelGGL(gpf_rank_kernel, dim3((N0 + 255) / 256), dim3(256), 0, s, norm, N0, B);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(gpf_compact_kernel, dim3(1), dim3(1024), 0, s, B.keep, norm, N0, kept, count, kept_norm);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
+}
+
+}  // extern "C"

@@ -295,14 +295,16 @@ hipError_t launch_best_refine(const float *src, const float *tgt, const float *s
 hipError_t launch_rigid(const float *A, const float *Bp, const float *w, int nb, int n, float *trans,
                         hipStream_t s);
 
-// training-mode forward pieces (training.hip)
+// the training forward's feature-similarity M (training.hip)
 // feats: the split normed copy [B][N][2][128] fp16 (H3) or normed [B][N][128] (f32)
 hipError_t launch_feat_sim(const void *feats, bool f32, int B, int N, const float *sigma, float *M, hipStream_t s);
-size_t sm_loss_partial_doubles(int B, int N);
-hipError_t launch_sm_loss(const float *M, const float *labels, int B, int N, int balanced, double *part, float *loss,
-                          hipStream_t s);
 
-// descriptor stage (descriptors.hip)
+// ---- cross-stage pieces --------------------------------------------------------
+// A row's entry points, workspace layouts, limits and launch code live in the
+// row's file (abi.hpp); declared here is only what a second row calls.
+
+// The uniform grid over a cloud (descriptors.hip), also ICP's target index (icp.hip).
+constexpr int GRID_KEY_BITS = 21;  // bits per axis of a grid cell key
 struct CloudStats {
     float mn[3], mx[3];
     double centroid[3];
@@ -326,112 +328,19 @@ struct GridBufs {
 void bind_grid(Carve &c, int n, GridBufs &G);
 size_t grid_workspace_bytes(int n);
 hipError_t build_grid(const float *pts, int n, double cell, double half, const GridBufs &G, hipStream_t s);
-hipError_t launch_radius_knn(const float *pts, int n, const GridBufs &G, double radius, int K, int *nbr, double *d2,
-                             int *cnt, hipStream_t s);
-hipError_t launch_normals(const float *pts, int n, const int *nbr, const int *cnt, int K, const GridBufs &G,
-                          int orient, const float *viewpoint, float *nrm, hipStream_t s);
-hipError_t launch_voxel_reduce(const float *pts, const float *nrm, int n, const GridBufs &G, float *opts, float *onrm,
-                               int *count, hipStream_t s);
-hipError_t launch_fpfh(const float *pts, const float *nrm, int n, const int *nbr, const int *cnt, const double *d2,
-                       int K, double *spfh, double *out, float *outn, hipStream_t s);
-int ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t *n_out, std::string &err);
+// the device error flags of a grid pass as a status (abi.hpp: fail), after draining the stream
+int grid_status(const GridBufs &G, hipStream_t s);
 
-// ICP refinement (icp.hip, the reference drivers' "+ICP" stage)
-constexpr int GRID_KEY_BITS = 21;       // bits per axis of a grid cell key (descriptors.hip: KEY_BITS)
-constexpr int ICP_CHUNK = 256;          // source points per partial row (the fixed summation order)
-constexpr int ICP_ONE_WG_MAX = 512;     // Ns up to which the loop runs in one workgroup (the measured crossover)
-size_t icp_workspace_bytes(int Ns, int Nt);
-// Builds the target's grid (G: for the caller's grid_status) and enqueues the
-// loop; one_wg: take the one-workgroup path where Ns <= ICP_ONE_WG_MAX.
-hipError_t launch_icp(const float *src, int Ns, const float *tgt, int Nt, const double *init, double max_distance,
-                      int max_iter, double rel_fitness, double rel_rmse, bool one_wg, float *trans_f32,
-                      pdsc_icp_result *res, int *corr, void *ws, GridBufs &G, hipStream_t s);
-
-// RANSAC on correspondences (ransac.hip, the drivers' RANSAC baseline / solver)
-constexpr int RANSAC_ROUND = 16384;     // hypotheses per round: part of the result's definition (pdsc_ransac_round)
-size_t ransac_workspace_bytes(int N);
-// Enqueues every round and the finish; H = max_iteration, sim = edge_similarity.
-hipError_t launch_ransac(const float *src, const float *tgt, int N, double max_distance, int ransac_n, double sim,
-                         int H, double confidence, unsigned long long seed, int refit, float *trans_f32, float *labels,
-                         pdsc_ransac_result *res, const pdsc_ransac_debug *debug, void *ws, hipStream_t s);
-
-// the refit over a point set of the caller's (ransac.hip: shares the finish kernel's scoring and Kabsch)
-hipError_t launch_refit_inliers(const double *pose, const float *src, const float *tgt, int N, double radius,
-                                double *trans, float *trans_f32, int *count, float *labels, hipStream_t s);
-
-// GC-RANSAC (gc_ransac.hip, f10): the grid neighbourhood, the exact per-cell graph cut, the solver
-constexpr int GC_MAX_ROWS = 1 << 18;  // as GPF_MAX_ROWS; also the LDS chunk rows of the one-pose scorer
-constexpr int GC_MAX_GRID = 1024;     // cells per axis: 6 axes of 10 bits in the 64-bit key
-constexpr int GC_WAVE_CELL = 64;      // cells up to this many rows: one wave, a row per lane
-constexpr int GC_LDS_CELL = 1024;     // up to this many: one workgroup in LDS; above: its global scratch
-size_t gc_grid_workspace_bytes(int N);
-hipError_t launch_gc_grid(const float *src, const float *tgt, int N, int G, int *order, int *cell_start, int *cell_of,
-                          int *n_cells, void *ws, hipStream_t s);
-size_t gc_label_workspace_bytes(int N);
-hipError_t launch_gc_label(const double *pose, const float *src, const float *tgt, int N, const int *order,
-                           const int *cell_start, const int *n_cells, double threshold, double lambda, float *labels,
-                           int *count, const pdsc_gc_label_debug *debug, void *ws, hipStream_t s);
-size_t gc_ransac_workspace_bytes(int N);
-// Enqueues the grid (lo != 0), every round with its LO steps and the finish; H = max_iteration.
-hipError_t launch_gc_ransac(const float *src, const float *tgt, int N, double threshold, double lambda, int G, int H,
-                            double confidence, unsigned long long seed, int lo, float *trans_f32, float *labels,
-                            pdsc_gc_ransac_result *res, const pdsc_gc_ransac_debug *debug, void *ws, hipStream_t s);
-
-// filtered-RANSAC front end (match_filter.hip, f7)
-constexpr int NN2_MAX_SPLIT = 16;  // column splits per row stripe the workspace is sized for
-int nn2_default_split(int Na, int Nb);
-size_t nn2_workspace_bytes(int Na, int Nb);
-// split: column splits per row stripe, 0 = nn2_default_split (clamped to the column tiles and NN2_MAX_SPLIT)
-hipError_t launch_nn2(const float *A, const float *B, int Na, int Nb, int D, int split, int *nn1, int *nn2, int *rev,
-                      void *ws, hipStream_t s);
-// rev == nullptr: only feat_dist
-hipError_t launch_match_ratio(const float *f0, const float *f1, int N0, int N1, int D, const int *nn1, const int *nn2,
-                              const int *rev, int *is_bb, float *feat_dist, float *norm, int *num_bb, hipStream_t s);
-// Rows pdsc_gpf_select accepts: a truncated cell of n rows costs n^2 word compares (gpf_rank_kernel), so one
-// cell holding every row costs N0^2 -- 6.9e10 at this limit, well under a second on 256 CUs.
-constexpr int GPF_MAX_ROWS = 1 << 18;
-size_t gpf_workspace_bytes(int N0, int G);
-hipError_t launch_gpf_select(const float *xyz0, const float *norm, const int *num_bb, int N0, int G, double factor,
-                             int *kept, int *count, float *kept_norm, const pdsc_gpf_debug *debug, void *ws,
-                             hipStream_t s);
-
-// PMC baseline (clique.hip, f8): adj is N rows of ceil(N / 64) 64-bit words
+// The consistency graph and the maximum clique (clique.hip), also TEASER's inlier
+// selection (teaser.hip): adj is N rows of ceil(N / 64) 64-bit words.
 constexpr int CLIQUE_MAX_N = 8192;                    // one wavefront holds a row in two words per lane
 constexpr long long CLIQUE_DEFAULT_BUDGET = 1 << 12;  // expanded nodes per root (DESIGN.md §7 "PMC baseline")
 hipError_t launch_consistency_graph(const float *corr_pos, int N, double thr, bool length, unsigned long long *adj,
                                     int *degree, hipStream_t s);
-int clique_depth();
-size_t clique_workspace_bytes(int N);
-// the same layout inside a caller's carver (teaser.hip); returns the base launch_max_clique takes as ws
+// the clique workspace's layout inside a caller's carver; returns the base launch_max_clique takes as ws
 void *reserve_clique(Carve &c, int N);
 // exact = false: the greedy lower bound alone
 hipError_t launch_max_clique(const unsigned long long *adj, int N, long long budget, bool exact, int *members,
                              pdsc_clique_result *res, float *labels, void *ws, hipStream_t s);
-
-// TEASER++ solvers (teaser.hip, f9).  Kdev != nullptr: the count is read on the device (0: return at entry) and
-// K is the capacity the launch is shaped for.
-constexpr int TEASER_MAX_N = CLIQUE_MAX_N;  // TIMs per thread of the one-workgroup rotation loop, LDS of the sort
-hipError_t launch_gnc_rotation(const double *A, const double *B, int K, const int *Kdev, double noise_bound,
-                               double factor, int max_iter, double cost_thr, double *R, double *weights, int *inliers,
-                               pdsc_gnc_info *info, hipStream_t s);
-size_t tls_workspace_bytes(int K);
-hipError_t launch_tls_translation(const double *src, const double *dst, int K, const int *Kdev, double noise_bound,
-                                  double *t, int *inliers, void *ws, hipStream_t s);
-size_t teaser_workspace_bytes(int N);
-hipError_t launch_teaser_solve(const float *src, const float *tgt, int N, double noise_bound, double factor,
-                               int max_iter, double cost_thr, long long budget, pdsc_teaser_result *res,
-                               float *trans_f32, float *labels, void *ws, hipStream_t s);
-
-// correspondence construction (corr.hip)
-// spectral-matching baseline (sm.hip)
-hipError_t launch_sm(const float *corr, const float *src, const float *tgt, int N, float sig2, int S, int iters,
-                     float *M, float *v, float *y, float *w, float *labels, float *trans, hipStream_t s);
-hipError_t launch_sm_matvec(const float *M, const float *v, int N, float *y, hipStream_t s);
-hipError_t launch_nn_argmin(const float *A, const float *B, int Na, int Nb, int D, unsigned long long *rowkey,
-                            unsigned long long *colkey, hipStream_t s);
-hipError_t launch_corr_build(const unsigned long long *rowkey, const unsigned long long *colkey,
-                             const float *src_xyz, const float *tgt_xyz, int Na, int mutual, const double *gt,
-                             double thr, int *corr, int *count, float *corr_pos, float *src_out, float *tgt_out,
-                             float *labels, hipStream_t s);
 
 }  // namespace pdsc

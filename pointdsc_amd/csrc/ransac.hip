@@ -31,6 +31,8 @@
 // Everything is enqueued up front; once the state's `done` word is set the
 // remaining rounds' kernels return at entry (as icp.hip).  No float atomics:
 // two calls are bitwise equal.
+#include <cmath>
+
 #include "ransac_shared.hpp"
 
 namespace pdsc {
@@ -149,25 +151,52 @@ __global__ __launch_bounds__(RANSAC_FIN) void refit_inliers_kernel(const double 
     if (count) count[0] = (int)n;
 }
 
-hipError_t launch_refit_inliers(const double *pose, const float *src, const float *tgt, int N, double radius,
-                                double *trans, float *trans_f32, int *count, float *labels, hipStream_t s) {
-    hipLaunchKernelGGL(refit_inliers_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, pose, src, tgt, N, radius * radius, trans,
-                       trans_f32, count, labels);
-    return hipGetLastError();
+}  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+int32_t pdsc_refit_inliers(const double *pose, const float *src, const float *tgt, int32_t N, double radius,
+                           double *trans, float *trans_f32, int32_t *count, float *labels, pdsc_stream_t stream) {
+    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d (need >= 1)", N);
+    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(PDSC_ERR_ARG, "radius %g must be > 0 and finite", radius);
+    if (!pose || !src || !tgt || !trans) return fail(PDSC_ERR_ARG, "null pointer");
+    hipLaunchKernelGGL(refit_inliers_kernel, dim3(1), dim3(RANSAC_FIN), 0, S_(stream), pose, src, tgt, N,
+                       radius * radius, trans, trans_f32, count, labels);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
 }
 
-// ------------------------------------------------------------------- launchers
-size_t ransac_workspace_bytes(int N) {
+int32_t pdsc_ransac_round(void) { return RANSAC_ROUND; }
+
+size_t pdsc_ransac_workspace_bytes(int32_t N) {
+    if (N < 1) return 0;
     Carve c(nullptr);
     RansacBufs B;
     bind_ransac(c, N, B);
     return c.off;
 }
 
-hipError_t launch_ransac(const float *src, const float *tgt, int N, double max_distance, int ransac_n, double sim,
-                         int H, double confidence, unsigned long long seed, int refit, float *trans_f32, float *labels,
-                         pdsc_ransac_result *res, const pdsc_ransac_debug *debug, void *ws, hipStream_t s) {
-    const int nchunks = (int)ransac_chunks(N);
+// Enqueues every round and the finish.
+int32_t pdsc_ransac_correspondence(const float *src, const float *tgt, int32_t N, double max_distance,
+                                   int32_t ransac_n, double edge_similarity, int32_t max_iteration,
+                                   double confidence, uint64_t seed, int32_t refit, float *trans_f32, float *labels,
+                                   pdsc_ransac_result *result, const pdsc_ransac_debug *debug, void *ws,
+                                   size_t ws_bytes, pdsc_stream_t stream) {
+    if (ransac_n != 3 && ransac_n != 4)
+        return fail(PDSC_ERR_UNSUPPORTED, "ransac_n=%d: only 3 and 4 are implemented", ransac_n);
+    if (N < ransac_n) return fail(PDSC_ERR_ARG, "N=%d < ransac_n=%d", N, ransac_n);
+    if (max_iteration < 1) return fail(PDSC_ERR_ARG, "max_iteration=%d (need >= 1)", max_iteration);
+    if (!(max_distance > 0.0) || !std::isfinite(max_distance))
+        return fail(PDSC_ERR_ARG, "max_distance %g must be > 0 and finite", max_distance);
+    if (!(confidence > 0.0 && confidence <= 1.0)) return fail(PDSC_ERR_ARG, "confidence %g not in (0, 1]", confidence);
+    if (!(edge_similarity >= 0.0 && edge_similarity <= 1.0))
+        return fail(PDSC_ERR_ARG, "edge_similarity %g not in [0, 1]", edge_similarity);
+    if (!src || !tgt || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_ransac_workspace_bytes(N)));
+    hipStream_t s = S_(stream);
+    const int H = max_iteration, nchunks = (int)ransac_chunks(N);
     Carve c(ws);
     RansacBufs B;
     bind_ransac(c, N, B);
@@ -180,19 +209,20 @@ hipError_t launch_ransac(const float *src, const float *tgt, int N, double max_d
         const RoundShape q = ransac_round_shape(H, r);
         if (ransac_n == 3)
             hipLaunchKernelGGL(ransac_hyp_kernel<3>, dim3(q.nwg), dim3(RANSAC_HWG), 0, s, src, tgt, N, q.base, H,
-                               (u64)seed, sim, B, dbg);
+                               (u64)seed, edge_similarity, B, dbg);
         else
             hipLaunchKernelGGL(ransac_hyp_kernel<4>, dim3(q.nwg), dim3(RANSAC_HWG), 0, s, src, tgt, N, q.base, H,
-                               (u64)seed, sim, B, dbg);
+                               (u64)seed, edge_similarity, B, dbg);
         hipLaunchKernelGGL(ransac_score_kernel<false>, dim3((q.nh + 63) / 64, nchunks), dim3(64), 0, s, src, tgt, N,
                            q.nwg, r2, B);
         hipLaunchKernelGGL(ransac_round_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, N, q.nwg, nchunks, r, H, ransac_n,
                            confidence, B, dbg);
-        HIP_RET(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(ransac_finish_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, src, tgt, N, r2, refit, B.st, trans_f32,
-                       labels, res);
-    return hipGetLastError();
+    hipLaunchKernelGGL(ransac_finish_kernel, dim3(1), dim3(RANSAC_FIN), 0, s, src, tgt, N, r2, refit ? 1 : 0, B.st,
+                       trans_f32, labels, result);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
 }
 
-}  // namespace pdsc
+}  // extern "C"

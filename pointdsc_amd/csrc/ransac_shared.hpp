@@ -12,13 +12,14 @@
 // Everything here is fp64 without contraction in a fixed order, so a caller
 // gets the same bits from either translation unit.
 #pragma once
+#include "abi.hpp"
 #include "pdsc_common.hpp"
 #include "pdsc_internal.hpp"
-#include "workspace.hpp"
 
 namespace pdsc {
 
 typedef unsigned long long u64;
+constexpr int RANSAC_ROUND = 16384;                    // hypotheses per round: part of the result's definition (pdsc_ransac_round)
 constexpr int RANSAC_HWG = 256;                        // hypotheses per workgroup of the hypothesis kernel
 constexpr int RANSAC_NWG = RANSAC_ROUND / RANSAC_HWG;  // its workgroups per full round
 constexpr int RANSAC_PCHUNK = 256;                     // points per scoring chunk (the fixed summation order)

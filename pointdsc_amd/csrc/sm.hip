@@ -14,6 +14,7 @@
 //   sm_select    one workgroup: the S-th largest key by bitwise bisection,
 //                ties to the lower index (the reference's argsort orders ties
 //                arbitrarily), labels and Kabsch weights
+#include "abi.hpp"
 #include "pdsc_internal.hpp"
 
 namespace pdsc {
@@ -171,24 +172,66 @@ __global__ __launch_bounds__(1024) void sm_select_kernel(const float *__restrict
     }
 }
 
-hipError_t launch_sm(const float *corr, const float *src, const float *tgt, int N, float sig2, int S, int iters,
-                     float *M, float *v, float *y, float *w, float *labels, float *trans, hipStream_t s) {
+// M [N][N] and the power iteration's v, y, w [N]
+struct SmBufs {
+    float *M, *v, *y, *w;
+};
+static void bind_sm(Carve &c, int N, SmBufs &W) {
+    W.M = c.take<float>((size_t)N * N);
+    W.v = c.take<float>((size_t)N);
+    W.y = c.take<float>((size_t)N);
+    W.w = c.take<float>((size_t)N);
+}
+
+}  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+size_t pdsc_spectral_matching_workspace_bytes(int32_t N) {
+    Carve c(nullptr);
+    SmBufs W;
+    bind_sm(c, N, W);
+    return c.off;
+}
+
+int32_t pdsc_spectral_matching(const float *corr_pos, const float *src, const float *tgt, int32_t N,
+                               double inlier_threshold, double top_ratio, int32_t iters, float *trans,
+                               float *labels, float *leading_eig, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    if (!corr_pos || !src || !tgt || !trans || !labels || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    if (N < 1 || N > 46340 || iters < 0 || !(top_ratio >= 0.0 && top_ratio <= 1.0) || !(inlier_threshold > 0.0))
+        return fail(PDSC_ERR_ARG, "N=%d iters=%d top_ratio=%g inlier_threshold=%g", N, iters, top_ratio,
+                    inlier_threshold);
+    RET_IF(need_ws(ws_bytes, pdsc_spectral_matching_workspace_bytes(N)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    SmBufs W;
+    bind_sm(c, N, W);
+    float *M = W.M, *v = leading_eig ? leading_eig : W.v, *y = W.y, *w = W.w;
+    const double sigma = inlier_threshold / 3.0;  // :34 (python float)
+    const float sig2 = (float)(sigma * sigma);    // tensor / python scalar -> fp32 divisor
+    const int S = (int)(N * top_ratio);           // int(leading_eig.shape[1] * top_ratio) (:46)
     const int nt = (N + SM_T - 1) / SM_T;
-    hipLaunchKernelGGL(sm_compat_kernel, dim3(nt, nt), dim3(256), 0, s, corr, N, sig2, M);
-    HIP_RET(hipGetLastError());
+    hipLaunchKernelGGL(sm_compat_kernel, dim3(nt, nt), dim3(256), 0, s, corr_pos, N, sig2, M);
+    HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(sm_fill_kernel, dim3((N + 255) / 256), dim3(256), 0, s, v, N, 1.0f);  // :39
     for (int it = 0; it < iters; ++it) {
         hipLaunchKernelGGL(sm_matvec_kernel, dim3((N + 3) / 4), dim3(256), 0, s, M, v, N, y);
         hipLaunchKernelGGL(sm_normalize_kernel, dim3(1), dim3(1024), 0, s, y, N, v);
     }
     hipLaunchKernelGGL(sm_select_kernel, dim3(1), dim3(1024), 0, s, v, N, S, labels, w);
-    HIP_RET(hipGetLastError());
-    return launch_rigid(src, tgt, w, 1, N, trans, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(launch_rigid(src, tgt, w, 1, N, trans, s));
+    return PDSC_OK;
 }
 
-hipError_t launch_sm_matvec(const float *M, const float *v, int N, float *y, hipStream_t s) {
-    hipLaunchKernelGGL(sm_matvec_kernel, dim3((N + 3) / 4), dim3(256), 0, s, M, v, N, y);
-    return hipGetLastError();
+int32_t pdsc_sm_matvec(const float *M, const float *v, int32_t N, float *y, pdsc_stream_t stream) {
+    if (!M || !v || !y) return fail(PDSC_ERR_ARG, "null pointer");
+    if (N < 1) return fail(PDSC_ERR_ARG, "N=%d", N);
+    hipLaunchKernelGGL(sm_matvec_kernel, dim3((N + 3) / 4), dim3(256), 0, S_(stream), M, v, N, y);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
 }
 
-}  // namespace pdsc
+}  // extern "C"

@@ -12,8 +12,10 @@
 // fixed tree (per-thread in slot order, xor butterfly inside a wave, the wave
 // partials in wave order), no atomics: two calls are bitwise equal.
 // DESIGN.md §7 "TEASER++" has the shapes and the numbers.
+#include <cmath>
+
+#include "abi.hpp"
 #include "pdsc_internal.hpp"
-#include "workspace.hpp"
 
 #pragma clang fp contract(off)
 
@@ -456,8 +458,8 @@ TeaserWs carve_teaser(Carve &k, int N) {
     return c;
 }
 
-}  // namespace
-
+// Kdev != nullptr (the solve): the count is read on the device (0: return at entry) and K is the capacity the
+// launch is shaped for.
 hipError_t launch_gnc_rotation(const double *A, const double *B, int K, const int *Kdev, double noise_bound,
                                double factor, int max_iter, double cost_thr, double *R, double *weights, int *inliers,
                                pdsc_gnc_info *info, hipStream_t s) {
@@ -477,45 +479,109 @@ hipError_t launch_gnc_rotation(const double *A, const double *B, int K, const in
     return hipGetLastError();
 }
 
-size_t tls_workspace_bytes(int K) {
-    Carve c(nullptr);
-    carve_tls(c, K);
-    return c.off;
-}
-
+// pre: carve_tls(K)'s slice
 hipError_t launch_tls_translation(const double *src, const double *dst, int K, const int *Kdev, double noise_bound,
-                                  double *t, int *inliers, void *ws, hipStream_t s) {
-    Carve c(ws);
-    hipLaunchKernelGGL(tls_axis_kernel, dim3(3), dim3(TB), 0, s, src, dst, K, Kdev, noise_bound, carve_tls(c, K), K, t);
+                                  double *t, int *inliers, double *pre, hipStream_t s) {
+    hipLaunchKernelGGL(tls_axis_kernel, dim3(3), dim3(TB), 0, s, src, dst, K, Kdev, noise_bound, pre, K, t);
     if (inliers)
         hipLaunchKernelGGL(tls_inlier_kernel, dim3((K + 255) / 256), dim3(256), 0, s, src, dst, K, Kdev, noise_bound, t,
                            inliers);
     return hipGetLastError();
 }
 
-size_t teaser_workspace_bytes(int N) {
+constexpr int TEASER_MAX_N = CLIQUE_MAX_N;  // TIMs per thread of the one-workgroup rotation loop, LDS of the sort
+
+int32_t check_teaser_count(const char *what, int32_t n) {
+    if (n < 1) return fail(PDSC_ERR_ARG, "%s=%d (need >= 1)", what, n);
+    if (n > TEASER_MAX_N) return fail(PDSC_ERR_UNSUPPORTED, "%s=%d > %d", what, n, TEASER_MAX_N);
+    return PDSC_OK;
+}
+
+int32_t check_noise_bound(double noise_bound) {
+    if (!(noise_bound > 0.0) || !std::isfinite(noise_bound))
+        return fail(PDSC_ERR_ARG, "noise_bound %g must be > 0 and finite", noise_bound);
+    return PDSC_OK;
+}
+
+int32_t check_gnc(double gnc_factor, int32_t max_iterations, double cost_threshold) {
+    if (!(gnc_factor > 1.0) || !std::isfinite(gnc_factor))
+        return fail(PDSC_ERR_ARG, "gnc_factor %g must be > 1 and finite", gnc_factor);
+    if (max_iterations < 1) return fail(PDSC_ERR_ARG, "max_iterations=%d (need >= 1)", max_iterations);
+    if (cost_threshold != cost_threshold) return fail(PDSC_ERR_ARG, "cost_threshold is NaN");
+    return PDSC_OK;
+}
+
+}  // namespace
+}  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+int32_t pdsc_gnc_tls_rotation(const double *src_tims, const double *dst_tims, int32_t K, double noise_bound,
+                              double gnc_factor, int32_t max_iterations, double cost_threshold, double *R,
+                              double *weights, int32_t *inliers, pdsc_gnc_info *info, pdsc_stream_t stream) {
+    RET_IF(check_teaser_count("K", K));
+    RET_IF(check_noise_bound(noise_bound));
+    RET_IF(check_gnc(gnc_factor, max_iterations, cost_threshold));
+    if (!src_tims || !dst_tims || !R) return fail(PDSC_ERR_ARG, "null pointer");
+    HIPCHK(launch_gnc_rotation(src_tims, dst_tims, K, nullptr, noise_bound, gnc_factor, max_iterations, cost_threshold,
+                               R, weights, inliers, info, S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_tls_translation_workspace_bytes(int32_t K) {
+    if (K < 1 || K > TEASER_MAX_N) return 0;
+    Carve c(nullptr);
+    carve_tls(c, K);
+    return c.off;
+}
+
+int32_t pdsc_tls_translation(const double *src, const double *dst, int32_t K, double noise_bound, double *t,
+                             int32_t *inliers, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    RET_IF(check_teaser_count("K", K));
+    RET_IF(check_noise_bound(noise_bound));
+    if (!src || !dst || !t || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_tls_translation_workspace_bytes(K)));
+    Carve c(ws);
+    HIPCHK(launch_tls_translation(src, dst, K, nullptr, noise_bound, t, inliers, carve_tls(c, K), S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_teaser_solve_workspace_bytes(int32_t N) {
+    if (N < 1 || N > TEASER_MAX_N) return 0;
     Carve k(nullptr);
     carve_teaser(k, N);
     return k.off;
 }
 
-hipError_t launch_teaser_solve(const float *src, const float *tgt, int N, double noise_bound, double factor,
-                               int max_iter, double cost_thr, long long budget, pdsc_teaser_result *res,
-                               float *trans_f32, float *labels, void *ws, hipStream_t s) {
+int32_t pdsc_teaser_solve(const float *src, const float *tgt, int32_t N, double noise_bound, double gnc_factor,
+                          int32_t max_iterations, double cost_threshold, int64_t node_budget,
+                          pdsc_teaser_result *result, float *trans_f32, float *labels, void *ws, size_t ws_bytes,
+                          pdsc_stream_t stream) {
+    RET_IF(check_teaser_count("N", N));
+    RET_IF(check_noise_bound(noise_bound));
+    RET_IF(check_gnc(gnc_factor, max_iterations, cost_threshold));
+    if (node_budget < 0) return fail(PDSC_ERR_ARG, "node_budget=%lld (need >= 0; 0: the default)", (long long)node_budget);
+    if (!src || !tgt || !result || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_teaser_solve_workspace_bytes(N)));
+    hipStream_t s = S_(stream);
+    const long long budget = node_budget ? (long long)node_budget : CLIQUE_DEFAULT_BUDGET;
     Carve k(ws);
     const TeaserWs c = carve_teaser(k, N);
     const dim3 rows((N + 255) / 256), b256(256);
     hipLaunchKernelGGL(pack_kernel, rows, b256, 0, s, src, tgt, N, c.corr);
-    HIP_RET(launch_consistency_graph(c.corr, N, 2.0 * noise_bound, true, c.adj, nullptr, s));
-    HIP_RET(launch_max_clique(c.adj, N, budget, true, c.members, c.cr, nullptr, c.clique, s));
+    HIPCHK(launch_consistency_graph(c.corr, N, 2.0 * noise_bound, true, c.adj, nullptr, s));
+    HIPCHK(launch_max_clique(c.adj, N, budget, true, c.members, c.cr, nullptr, c.clique, s));
     hipLaunchKernelGGL(tim_kernel, rows, b256, 0, s, src, tgt, N, c.members, c.cr, c.A, c.B, c.kdev);
-    HIP_RET(launch_gnc_rotation(c.A, c.B, N, c.kdev, noise_bound, factor, max_iter, cost_thr, c.R, nullptr, c.rinl,
-                                c.info, s));
+    HIPCHK(launch_gnc_rotation(c.A, c.B, N, c.kdev, noise_bound, gnc_factor, max_iterations, cost_threshold, c.R, nullptr,
+                               c.rinl, c.info, s));
     hipLaunchKernelGGL(rotate_kernel, rows, b256, 0, s, src, tgt, N, c.members, c.kdev, c.R, c.S, c.D);
-    HIP_RET(launch_tls_translation(c.S, c.D, N, c.kdev, noise_bound, c.t, c.tinl, c.pre, s));
+    HIPCHK(launch_tls_translation(c.S, c.D, N, c.kdev, noise_bound, c.t, c.tinl, c.pre, s));
     hipLaunchKernelGGL(teaser_finish_kernel, dim3(1), b256, 0, s, N, c.members, c.cr, c.kdev, c.R, c.t, c.info, c.rinl,
-                       c.tinl, res, trans_f32, labels);
-    return hipGetLastError();
+                       c.tinl, result, trans_f32, labels);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
 }
 
-}  // namespace pdsc
+}  // extern "C"

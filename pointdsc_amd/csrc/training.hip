@@ -8,6 +8,7 @@
 //   sm_loss    SpectralMatchingLoss (libs/loss.py:115-139), balanced or MSE, in
 //              fp64 partial sums: one workgroup per (pair, 64-row strip), then a
 //              fixed-order per-pair reduction
+#include "abi.hpp"
 #include "attention_h3.hpp"
 
 namespace pdsc {
@@ -143,14 +144,37 @@ __global__ void sm_loss_final_kernel(const double *__restrict__ part, int B, int
     loss[0] = balanced ? (float)(total / B) : (float)(mse / ((double)B * N * N));
 }
 
-size_t sm_loss_partial_doubles(int B, int N) { return (size_t)B * ((N + SML_ROWS - 1) / SML_ROWS) * 4; }
-
-hipError_t launch_sm_loss(const float *M, const float *labels, int B, int N, int balanced, double *part, float *loss,
-                          hipStream_t s) {
-    const int nstrip = (N + SML_ROWS - 1) / SML_ROWS;
-    hipLaunchKernelGGL(sm_loss_partial_kernel, dim3(nstrip, B), dim3(256), 0, s, M, labels, N, part);
-    hipLaunchKernelGGL(sm_loss_final_kernel, dim3(1), dim3(64), 0, s, part, B, N, nstrip, balanced, loss);
-    return hipGetLastError();
+// the partial rows [B][strips][4]
+static double *bind_sm_loss(Carve &c, int B, int N) {
+    return c.take<double>((size_t)B * ((N + SML_ROWS - 1) / SML_ROWS) * 4);
 }
 
 }  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+size_t pdsc_spectral_matching_loss_workspace_bytes(int32_t B, int32_t N) {
+    if (B < 1 || N < 1) return 0;
+    Carve c(nullptr);
+    bind_sm_loss(c, B, N);
+    return c.off;
+}
+
+int32_t pdsc_spectral_matching_loss(const float *M, const float *gt_labels, int32_t B, int32_t N, int32_t balanced,
+                                    float *loss, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    if (!M || !gt_labels || !loss || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    if (B < 1 || N < 1) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
+    RET_IF(need_ws(ws_bytes, pdsc_spectral_matching_loss_workspace_bytes(B, N)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    double *part = bind_sm_loss(c, B, N);
+    const int nstrip = (N + SML_ROWS - 1) / SML_ROWS;
+    hipLaunchKernelGGL(sm_loss_partial_kernel, dim3(nstrip, B), dim3(256), 0, s, M, gt_labels, N, part);
+    hipLaunchKernelGGL(sm_loss_final_kernel, dim3(1), dim3(64), 0, s, part, B, N, nstrip, balanced, loss);
+    HIPCHK(hipGetLastError());
+    return PDSC_OK;
+}
+
+}  // extern "C"
