@@ -985,6 +985,145 @@ int32_t pdsc_gc_ransac(const float *src, const float *tgt, int32_t N, double thr
                        const pdsc_gc_ransac_debug *debug /* HOST struct of device pointers, may be NULL */,
                        void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
 
+/* --------------------------- f11 information matrix (multiway registration) --
+ * open3d's get_information_matrix_from_point_clouds, which the multiway driver
+ * calls once per fragment pair (multiway/test_multi_ate.py:141-146; its [5][5]
+ * entry decides whether the pair becomes a loop-closure edge, :147) and at the
+ * last scale of multi_scale_icp (:69-72).  open3d's algorithm restated (parity
+ * with open3d itself is unpinned).  The correspondences are exactly those of
+ * pdsc_icp_point_to_point's evaluate(trans): q = R p + t in fp64, the nearest
+ * target point with fp64 d^2 <= max_distance^2, ties to the lower target index
+ * (the same device function).  Every correspondence adds G^T G for its target
+ * point (x, y, z) -- promoted to fp64, NOT transformed -- and the rows
+ * (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1): info is built
+ * from 10 sums (the count, sum t, the six entries of sum t t^T), each reduced
+ * per 256-point source chunk by xor shuffles and an LDS stage and then over the
+ * chunks in order by one wave -- no float atomics, two calls are bitwise equal.
+ * info[0][0] = Syy + Szz, info[1][1] = Sxx + Szz, info[2][2] = Sxx + Syy,
+ * info[5][5] = n_corr; without a correspondence info is the zero matrix.
+ * Like f5 the call synchronises `stream` once at the end to report the grid
+ * error (target extent / max_distance >= 2^21 cells: PDSC_ERR_ARG).  Other
+ * errors (PDSC_ERR_ARG, on the host before any device work): Ns or Nt < 1,
+ * max_distance <= 0 or not finite, null source / target / result / workspace,
+ * a workspace that is too small.                                             */
+typedef struct pdsc_information_result { /* device memory, written by the call */
+    double  info[36];                    /* row-major [6,6] */
+    int32_t n_corr;
+    int32_t pad;
+} pdsc_information_result;
+size_t  pdsc_information_matrix_workspace_bytes(int32_t Ns, int32_t Nt);
+int32_t pdsc_information_matrix(const float *source, int32_t Ns, const float *target, int32_t Nt,
+                                const double *trans /* device double[16], NULL = identity */, double max_distance,
+                                pdsc_information_result *result,
+                                int32_t *corr /* [Ns]: target index or -1, may be NULL */, void *workspace,
+                                size_t workspace_bytes, pdsc_stream_t stream);
+
+/* ------------------------------ f12 pose-graph optimisation (multiway) -------
+ * open3d's global_optimization with GlobalOptimizationLevenbergMarquardt, as
+ * multiway/test_multi_ate.py:166-174, 217-224 and multiway/optimize_posegraph.py
+ * call it: the step that throws out false loop closures.  open3d's algorithm
+ * restated (parity with open3d itself is unpinned); what follows is the contract.
+ * All arithmetic is fp64, no float atomics, every sum in a fixed order: two
+ * calls are bitwise equal.  The whole two-pass optimisation is one launch of
+ * one workgroup.  Every pointer but options / criteria is device memory.
+ *   Inputs      poses [n,16]: node frame -> world, row-major, updated in place
+ *               (the last row is taken to be 0 0 0 1).  Edge k: edge_src[k],
+ *               edge_tgt[k]; edge_trans [E,16] maps the source node's frame into
+ *               the target node's (~ pose_t^-1 pose_s, test_multi_ate.py:
+ *               129-135); edge_info [E,36], taken to be symmetric; edge_uncertain
+ *               [E] (non-zero: a loop closure the line process may switch off).
+ *   Residual    e = vec6(X^-1 Tt^-1 Ts), vec6(M) = (atan2(M21, M22), atan2(-M20,
+ *               sy), atan2(M10, M00), M03, M13, M23), sy = sqrt(M00^2 + M10^2);
+ *               sy < 1e-6: (atan2(-M12, M11), atan2(-M20, sy), 0).  Inverses are
+ *               (R^T, -R^T t); every product is ((a0 b0 + a1 b1) + a2 b2) (+ a3).
+ *   Jacobians   D_i the se(3) generators (rotations about x, y, z, translations):
+ *               column i of Js = lin6(X^-1 Tt^-1 D_i Ts), of Jt = lin6(X^-1 Tt^-1
+ *               (-D_i) Ts) = -Js; lin6(M) = ((M21 - M12) / 2, (M02 - M20) / 2,
+ *               (M10 - M01) / 2, M03, M13, M23).
+ *   Line proc.  mu = preference_loop_closure max_correspondence_distance^2 mean
+ *               over the pass's uncertain edges of info[5][5] (0 without any);
+ *               l = 1 for certain edges, (mu / (mu + e^T L e))^2 for uncertain
+ *               ones (1 where mu + e^T L e is not positive).
+ *               F = sum l e^T L e + mu sum over uncertain edges (sqrt(l) - 1)^2.
+ *   System      B = Js^T L Js per edge (entries r <= c computed and mirrored, so H
+ *               is symmetric bit for bit), g = Js^T L e: H_ss += l B, H_tt += l B,
+ *               H_st -= l B, H_ts -= l B, b_s -= l g, b_t += l g, each 6x6 block
+ *               summed over its edges in ascending edge index; then the reference
+ *               node's rows and columns are zeroed, their diagonal 1, its b 0.
+ *   LM          lambda = 1e-5 max diag H, nu = 2; nothing runs if max b <
+ *               min_right_term or F < min_residual.  At most max_iteration outer
+ *               iterations, each at most max_iteration_lm + 1 times (one more
+ *               stops the pass): solve (H + lambda I) delta = b (blocked Cholesky
+ *               on 6x6 blocks); stop if |delta| < min_relative_increment (|x| +
+ *               min_relative_increment), x the stacked vec6 of the poses; trial
+ *               poses Exp(delta_i) pose_i, Exp(d) = Rz(d2) Ry(d1) Rx(d0) with
+ *               translation d3..5; rho = (F - F_new) / (delta . (lambda delta + b)
+ *               + 1e-3), F_new under the current l.  rho > 0: stop if F - F_new <
+ *               min_relative_residual_increment F, else accept the trial poses,
+ *               recompute l, F under the new l, H and b, lambda *= max(1/3, 1 -
+ *               (2 rho - 1)^3), nu = 2, and stop if max b < min_right_term.
+ *               Otherwise lambda *= nu, nu *= 2.  An outer iteration ends with
+ *               the F < min_residual test.
+ *   Two passes  over all edges; then edge_keep = !uncertain || confidence >
+ *               edge_prune_threshold; then over the kept edges, mu and l
+ *               recomputed over them.  confidence [E] = the final l (a dropped
+ *               edge keeps its pass-1 value).
+ *   Failure     a Cholesky pivot that is not positive and finite sets
+ *               solver_failed: the loop stops, the last accepted poses stay.
+ *   Errors      on the host, before any device work: PDSC_ERR_ARG for n < 1, E <
+ *               0, reference_node outside [0, n), null required pointers (the
+ *               edge arrays, confidence and edge_keep may be NULL when E = 0),
+ *               max_correspondence_distance <= 0, a negative preference, a
+ *               workspace that is too small; PDSC_ERR_UNSUPPORTED for n > 256 or
+ *               E > 32768 (the workspace query returns 0 there: the dense H and
+ *               its factor are 2 x 18.9 MB at n = 256).  An edge with src == tgt
+ *               or an id outside [0, n) is found on the device and reported
+ *               (PDSC_ERR_ARG) after the call's single final synchronise; nothing
+ *               is optimised then.
+ * pdsc_pose_graph_linearize is one linearisation by the same device functions:
+ * given poses, edges, l (line_process [E], NULL = all 1) and mu it returns
+ * residual [E,6], objective [1] = F, H [6n,6n] and b [6n].                    */
+#define PDSC_PG_MAX_ITERATION 100
+#define PDSC_PG_MAX_ITERATION_LM 20
+#define PDSC_PG_MIN_RELATIVE_INCREMENT 1e-6
+#define PDSC_PG_MIN_RELATIVE_RESIDUAL_INCREMENT 1e-6
+#define PDSC_PG_MIN_RIGHT_TERM 1e-6
+#define PDSC_PG_MIN_RESIDUAL 1e-6
+typedef struct pdsc_pose_graph_options { /* HOST; open3d's GlobalOptimizationOption */
+    double  max_correspondence_distance;
+    double  edge_prune_threshold;
+    double  preference_loop_closure;
+    int32_t reference_node;
+    int32_t pad;
+} pdsc_pose_graph_options;
+typedef struct pdsc_pose_graph_criteria { /* HOST; open3d's GlobalOptimizationConvergenceCriteria */
+    int32_t max_iteration;
+    int32_t max_iteration_lm;
+    double  min_relative_increment;
+    double  min_relative_residual_increment;
+    double  min_right_term;
+    double  min_residual;
+} pdsc_pose_graph_criteria;
+typedef struct pdsc_pose_graph_result { /* device memory, written by the call */
+    double  objective[2];               /* F at the end of each pass */
+    double  mu[2];                      /* of each pass */
+    int32_t iterations[2];              /* outer iterations of each pass */
+    int32_t edges_kept;
+    int32_t solver_failed;
+} pdsc_pose_graph_result;
+size_t  pdsc_pose_graph_workspace_bytes(int32_t n, int32_t E);
+int32_t pdsc_pose_graph_optimize(double *poses, int32_t n, const int32_t *edge_src, const int32_t *edge_tgt,
+                                 const double *edge_trans, const double *edge_info, const int32_t *edge_uncertain,
+                                 int32_t E, const pdsc_pose_graph_options *options,
+                                 const pdsc_pose_graph_criteria *criteria /* NULL: the defaults above */,
+                                 double *confidence, int32_t *edge_keep, pdsc_pose_graph_result *result,
+                                 void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+int32_t pdsc_pose_graph_linearize(const double *poses, int32_t n, const int32_t *edge_src, const int32_t *edge_tgt,
+                                  const double *edge_trans, const double *edge_info, const int32_t *edge_uncertain,
+                                  int32_t E, const double *line_process, double mu, int32_t reference_node,
+                                  double *residual, double *objective, double *H, double *b, void *workspace,
+                                  size_t workspace_bytes, pdsc_stream_t stream);
+
 /* ----------------------------------------------- full testing forward ------
  * PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197)
  * for B independent pairs: compat -> encoder -> classifier -> seeds -> kNN ->

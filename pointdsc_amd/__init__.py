@@ -10,7 +10,9 @@ are the fork's correspondence filters (MFR, GPF) and its filtered RANSAC ``FR``;
 (consistency graph + maximum clique); ``pointdsc_amd.teaser`` is the fork's
 ``TEASER`` (graph, clique, GNC-TLS rotation, TLS translation);
 ``pointdsc_amd.gc_ransac`` is its ``GC`` (GC-RANSAC on the grid neighbourhood, the
-exact per-cell graph cut; ``GCRANSAC`` is the baseline); the C ABI is ``include/pdsc.h`` /
+exact per-cell graph cut; ``GCRANSAC`` is the baseline); ``pointdsc_amd.multiway``
+is multiway registration around the forward (information matrix, multi-scale ICP,
+pose-graph optimisation with loop-closure pruning, ATE); the C ABI is ``include/pdsc.h`` /
 ``pointdsc_amd/libpdsc.so``.
 """
 __version__ = "0.1.0"

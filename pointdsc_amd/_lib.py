@@ -111,6 +111,30 @@ class PdscGcRansacDebug(ctypes.Structure):
     _fields_ = [("samples", vp), ("count", vp), ("score", vp), ("trans", vp)]
 
 
+class PdscInformationResult(ctypes.Structure):
+    """``struct pdsc_information_result`` (include/pdsc.h): 296 bytes of device memory."""
+    _fields_ = [("info", c_double * 36), ("n_corr", c_int32), ("pad", c_int32)]
+
+
+class PdscPoseGraphOptions(ctypes.Structure):
+    """``struct pdsc_pose_graph_options`` (include/pdsc.h): a host struct."""
+    _fields_ = [("max_correspondence_distance", c_double), ("edge_prune_threshold", c_double),
+                ("preference_loop_closure", c_double), ("reference_node", c_int32), ("pad", c_int32)]
+
+
+class PdscPoseGraphCriteria(ctypes.Structure):
+    """``struct pdsc_pose_graph_criteria`` (include/pdsc.h): a host struct; open3d's defaults."""
+    _fields_ = [("max_iteration", c_int32), ("max_iteration_lm", c_int32), ("min_relative_increment", c_double),
+                ("min_relative_residual_increment", c_double), ("min_right_term", c_double),
+                ("min_residual", c_double)]
+
+
+class PdscPoseGraphResult(ctypes.Structure):
+    """``struct pdsc_pose_graph_result`` (include/pdsc.h): 48 bytes of device memory."""
+    _fields_ = [("objective", c_double * 2), ("mu", c_double * 2), ("iterations", c_int32 * 2),
+                ("edges_kept", c_int32), ("solver_failed", c_int32)]
+
+
 # enum pdsc_edge_mode (include/pdsc.h)
 EDGE_MODES = {"squared": 0, "length": 1}
 
@@ -213,6 +237,13 @@ _PROTOS = {
     "pdsc_gc_ransac_workspace_bytes": (c_size_t, [c_int32]),
     "pdsc_gc_ransac": (c_int32, [vp, vp, c_int32, c_double, c_double, c_int32, c_int32, c_double, ctypes.c_uint64,
                                  c_int32, vp, vp, vp, ctypes.POINTER(PdscGcRansacDebug), vp, c_size_t, vp]),
+    "pdsc_information_matrix_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "pdsc_information_matrix": (c_int32, [vp, c_int32, vp, c_int32, vp, c_double, vp, vp, vp, c_size_t, vp]),
+    "pdsc_pose_graph_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "pdsc_pose_graph_optimize": (c_int32, [vp, c_int32, vp, vp, vp, vp, vp, c_int32, vp, vp, vp, vp, vp, vp, c_size_t,
+                                           vp]),
+    "pdsc_pose_graph_linearize": (c_int32, [vp, c_int32, vp, vp, vp, vp, vp, c_int32, vp, c_double, c_int32, vp, vp,
+                                            vp, vp, vp, c_size_t, vp]),
     "pdsc_forward_training_workspace_bytes": (c_size_t, [CFG, c_int32, c_int32]),
     "pdsc_range_status": (c_int32, [vp, c_int32, ctypes.POINTER(c_int32), vp]),
     "pdsc_range_poll": (c_int32, [vp, c_int32, vp]),

@@ -73,12 +73,79 @@ PDSC_DEV void icp_init_state(IcpState *st, const double *init) {
     st->pad = 0;
 }
 
+// A source point's correspondence under T: q = R p + t in fp64 and the nearest
+// target point with d^2 <= r2 (ties: the lower index), best = -1 without one.
+// The 27 cells around the query are 9 (x, y) columns of up to 3 cells
+// consecutive in key order: one binary search in ukey per column, then the
+// occupied cells' runs.  Shared by evaluate (f5) and the information matrix (f11).
+struct IcpHit {
+    int best;
+    double d2, qx, qy, qz, tx, ty, tz;  // d2 and the target point (fp64) where best >= 0
+};
+PDSC_DEV IcpHit icp_nearest(const float *__restrict__ src, int i, const float *__restrict__ tgt,
+                            const CloudStats *__restrict__ gs, double cell, double r2, const GridView &g,
+                            const double *T) {
+    const double x = src[3 * (size_t)i], y = src[3 * (size_t)i + 1], z = src[3 * (size_t)i + 2];
+    const double qx = (T[0] * x + T[1] * y) + T[2] * z + T[3];
+    const double qy = (T[4] * x + T[5] * y) + T[6] * z + T[7];
+    const double qz = (T[8] * x + T[9] * y) + T[10] * z + T[11];
+    // signed cell coordinates (cell_of's formula, not clamped); NaN fails the range test
+    const double fx = floor((qx - (double)gs->mn[0]) / cell), fy = floor((qy - (double)gs->mn[1]) / cell),
+                 fz = floor((qz - (double)gs->mn[2]) / cell);
+    const double top = (double)(ICP_KEY_MAX + 1);
+    int best = -1;
+    double bd = 0.0, bx = 0.0, by = 0.0, bz = 0.0;
+    if (fx >= -1.0 && fx <= top && fy >= -1.0 && fy <= top && fz >= -1.0 && fz <= top) {
+        const long long cx = (long long)fx, cy = (long long)fy, cz = (long long)fz;
+        const long long z0 = cz > 0 ? cz - 1 : 0, z1 = cz < ICP_KEY_MAX ? cz + 1 : ICP_KEY_MAX;
+        const int nr = *g.nruns;
+        for (int c = 0; c < 9; ++c) {
+            const long long ix = cx + c / 3 - 1, iy = cy + c % 3 - 1;
+            if (ix < 0 || iy < 0 || ix > ICP_KEY_MAX || iy > ICP_KEY_MAX || z0 > z1) continue;
+            const u64 khi = icp_key(ix, iy, z1);
+            for (int u = icp_lower_bound(g.ukey, nr, icp_key(ix, iy, z0)); u < nr && g.ukey[u] <= khi; ++u) {
+                const int s = g.ustart[u], m = g.ucount[u];
+                for (int j = s; j < s + m; ++j) {
+                    const int pi = g.sidx[j];
+                    const double tx = tgt[3 * (size_t)pi], ty = tgt[3 * (size_t)pi + 1], tz = tgt[3 * (size_t)pi + 2];
+                    const double dx = tx - qx, dy = ty - qy, dz = tz - qz;
+                    const double d2 = dx * dx + dy * dy + dz * dz;
+                    if (d2 <= r2 && (best < 0 || d2 < bd || (d2 == bd && pi < best))) {
+                        best = pi;
+                        bd = d2;
+                        bx = tx;
+                        by = ty;
+                        bz = tz;
+                    }
+                }
+            }
+        }
+    }
+    return IcpHit{best, bd, qx, qy, qz, bx, by, bz};
+}
+
+// The fixed-order sum of a chunk's NS per-point values v (thread t of 256, all
+// of them calling together: it holds workgroup barriers): xor shuffles inside
+// each wave, the four waves' rows through red ([4][NS] of LDS) in wave order,
+// to part[NS chunk ..] (chunk < nchunks).
+template <int NS>
+PDSC_DEV void icp_reduce_chunk(const double (&v)[NS], int t, int chunk, int nchunks, double *red, double *part) {
+    const int w = t >> 6;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const double s = wave_sum(v[j]);
+        if ((t & 63) == 0) red[w * NS + j] = s;
+    }
+    __syncthreads();
+    if (t < NS && chunk < nchunks)
+        part[(size_t)chunk * NS + t] = ((red[t] + red[NS + t]) + red[2 * NS + t]) + red[3 * NS + t];
+    __syncthreads();  // red is free for the next chunk
+}
+
 // evaluate(T) for source chunk `chunk` (points 256 chunk + t, t = 0 .. 255, by
 // the 256 threads that call this together with every other thread of the
 // workgroup: it holds workgroup barriers).  red: the chunk's [4][17] LDS stage;
-// the chunk's 17 sums go to part[17 chunk ..] (chunk < nchunks).  The 27 cells
-// around the query are 9 (x, y) columns of up to 3 cells consecutive in key
-// order: one binary search in ukey per column, then the occupied cells' runs.
+// the chunk's 17 sums go to part[17 chunk ..] (chunk < nchunks).
 PDSC_DEV void icp_eval_chunk(const float *__restrict__ src, int Ns, const float *__restrict__ tgt,
                              const CloudStats *__restrict__ gs, double cell, double r2, const GridView &g,
                              const double *T, int chunk, int nchunks, int t, double *red, double *part,
@@ -88,51 +155,14 @@ PDSC_DEV void icp_eval_chunk(const float *__restrict__ src, int Ns, const float 
 #pragma unroll
     for (int j = 0; j < ICP_NSUM; ++j) v[j] = 0.0;
     if (i < Ns) {
-        const double x = src[3 * (size_t)i], y = src[3 * (size_t)i + 1], z = src[3 * (size_t)i + 2];
-        const double qx = (T[0] * x + T[1] * y) + T[2] * z + T[3];
-        const double qy = (T[4] * x + T[5] * y) + T[6] * z + T[7];
-        const double qz = (T[8] * x + T[9] * y) + T[10] * z + T[11];
-        // signed cell coordinates (cell_of's formula, not clamped); NaN fails the range test
-        const double fx = floor((qx - (double)gs->mn[0]) / cell), fy = floor((qy - (double)gs->mn[1]) / cell),
-                     fz = floor((qz - (double)gs->mn[2]) / cell);
-        const double top = (double)(ICP_KEY_MAX + 1);
-        int best = -1;
-        double bd = 0.0, bx = 0.0, by = 0.0, bz = 0.0;
-        if (fx >= -1.0 && fx <= top && fy >= -1.0 && fy <= top && fz >= -1.0 && fz <= top) {
-            const long long cx = (long long)fx, cy = (long long)fy, cz = (long long)fz;
-            const long long z0 = cz > 0 ? cz - 1 : 0, z1 = cz < ICP_KEY_MAX ? cz + 1 : ICP_KEY_MAX;
-            const int nr = *g.nruns;
-            for (int c = 0; c < 9; ++c) {
-                const long long ix = cx + c / 3 - 1, iy = cy + c % 3 - 1;
-                if (ix < 0 || iy < 0 || ix > ICP_KEY_MAX || iy > ICP_KEY_MAX || z0 > z1) continue;
-                const u64 khi = icp_key(ix, iy, z1);
-                for (int u = icp_lower_bound(g.ukey, nr, icp_key(ix, iy, z0)); u < nr && g.ukey[u] <= khi; ++u) {
-                    const int s = g.ustart[u], m = g.ucount[u];
-                    for (int j = s; j < s + m; ++j) {
-                        const int pi = g.sidx[j];
-                        const double tx = tgt[3 * (size_t)pi], ty = tgt[3 * (size_t)pi + 1], tz = tgt[3 * (size_t)pi + 2];
-                        const double dx = tx - qx, dy = ty - qy, dz = tz - qz;
-                        const double d2 = dx * dx + dy * dy + dz * dz;
-                        if (d2 <= r2 && (best < 0 || d2 < bd || (d2 == bd && pi < best))) {
-                            best = pi;
-                            bd = d2;
-                            bx = tx;
-                            by = ty;
-                            bz = tz;
-                        }
-                    }
-                }
-            }
-        }
-        if (corr) corr[i] = best;
-        if (best >= 0) {
+        const IcpHit h = icp_nearest(src, i, tgt, gs, cell, r2, g, T);
+        if (corr) corr[i] = h.best;
+        if (h.best >= 0) {
             const double c0 = gs->centroid[0], c1 = gs->centroid[1], c2 = gs->centroid[2];
-            const double ax = qx - c0, ay = qy - c1, az = qz - c2;
-            bx -= c0;
-            by -= c1;
-            bz -= c2;
+            const double ax = h.qx - c0, ay = h.qy - c1, az = h.qz - c2;
+            const double bx = h.tx - c0, by = h.ty - c1, bz = h.tz - c2;
             v[0] = 1.0;
-            v[1] = bd;
+            v[1] = h.d2;
             v[2] = ax;
             v[3] = ay;
             v[4] = az;
@@ -150,17 +180,7 @@ PDSC_DEV void icp_eval_chunk(const float *__restrict__ src, int Ns, const float 
             v[16] = az * bz;
         }
     }
-    const int w = t >> 6;
-#pragma unroll
-    for (int j = 0; j < ICP_NSUM; ++j) {
-        const double s = wave_sum(v[j]);
-        if ((t & 63) == 0) red[w * ICP_NSUM + j] = s;
-    }
-    __syncthreads();
-    if (t < ICP_NSUM && chunk < nchunks)
-        part[(size_t)chunk * ICP_NSUM + t] =
-            ((red[t] + red[ICP_NSUM + t]) + red[2 * ICP_NSUM + t]) + red[3 * ICP_NSUM + t];
-    __syncthreads();  // red is free for the next chunk
+    icp_reduce_chunk<ICP_NSUM>(v, t, chunk, nchunks, red, part);
 }
 
 // One wave, after evaluation k (k = 0: of init): the chunks' rows summed in
@@ -281,6 +301,69 @@ __global__ __launch_bounds__(ICP_WG) void icp_one_wg_kernel(const float *__restr
     }
 }
 
+// ------------------------------------------- f11: the information matrix
+// open3d's GetInformationMatrixFromPointClouds on evaluate(T)'s correspondences:
+// per correspondence the target point (x, y, z) in fp64, not transformed, adds
+// G^T G for G's rows (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1),
+// which is 10 sums: the count, sum t, and the six entries of sum t t^T.
+constexpr int INFO_NSUM = 10;  // count, x, y, z, xx, xy, xz, yy, yz, zz
+
+__global__ __launch_bounds__(ICP_CHUNK) void info_eval_kernel(const float *__restrict__ src, int Ns,
+                                                              const float *__restrict__ tgt, const CloudStats *gs,
+                                                              double cell, double r2, GridView g, const double *trans,
+                                                              int nchunks, double *part, int *corr) {
+    __shared__ double red[4 * INFO_NSUM];
+    __shared__ double T[16];
+    const int t = threadIdx.x;
+    if (t < 16) T[t] = trans ? trans[t] : (t % 5 == 0 ? 1.0 : 0.0);
+    __syncthreads();
+    const int i = blockIdx.x * ICP_CHUNK + t;
+    double v[INFO_NSUM];
+#pragma unroll
+    for (int j = 0; j < INFO_NSUM; ++j) v[j] = 0.0;
+    if (i < Ns) {
+        const IcpHit h = icp_nearest(src, i, tgt, gs, cell, r2, g, T);
+        if (corr) corr[i] = h.best;
+        if (h.best >= 0) {
+            v[0] = 1.0;
+            v[1] = h.tx;
+            v[2] = h.ty;
+            v[3] = h.tz;
+            v[4] = h.tx * h.tx;
+            v[5] = h.tx * h.ty;
+            v[6] = h.tx * h.tz;
+            v[7] = h.ty * h.ty;
+            v[8] = h.ty * h.tz;
+            v[9] = h.tz * h.tz;
+        }
+    }
+    icp_reduce_chunk<INFO_NSUM>(v, t, blockIdx.x, nchunks, red, part);
+}
+
+// One wave: the chunks' rows summed in chunk order, then the 36 entries.
+__global__ __launch_bounds__(64) void info_finish_kernel(const double *part, int nchunks,
+                                                         pdsc_information_result *res) {
+    const int lane = threadIdx.x;
+    double acc = 0.0;
+    if (lane < INFO_NSUM)
+        for (int c = 0; c < nchunks; ++c) acc += part[(size_t)c * INFO_NSUM + lane];
+    double S[INFO_NSUM];
+#pragma unroll
+    for (int j = 0; j < INFO_NSUM; ++j) S[j] = __shfl(acc, j);
+    if (lane != 0) return;
+    const double n = S[0], x = S[1], y = S[2], z = S[3], xx = S[4], xy = S[5], xz = S[6], yy = S[7], yz = S[8],
+                 zz = S[9];
+    const double M[36] = {yy + zz, -xy, -xz, 0.0, -z,  y,    //
+                          -xy, xx + zz, -yz, z,   0.0, -x,   //
+                          -xz, -yz, xx + yy, -y,  x,   0.0,  //
+                          0.0, z,   -y,  n,   0.0, 0.0,      //
+                          -z,  0.0, x,   0.0, n,   0.0,      //
+                          y,   -x,  0.0, 0.0, 0.0, n};
+    for (int i = 0; i < 36; ++i) res->info[i] = n > 0.0 ? M[i] : 0.0;  // no correspondence: +0 everywhere
+    res->n_corr = (int)n;
+    res->pad = 0;
+}
+
 // ------------------------------------------------------------------ launchers
 static size_t icp_chunks(int Ns) { return ((size_t)Ns + ICP_CHUNK - 1) / ICP_CHUNK; }
 
@@ -300,6 +383,16 @@ static void bind_icp(Carve &c, int Ns, int Nt, IcpBufs &I) {
 static bool icp_one_wg() {
     const char *e = getenv("PDSC_ICP_ONE_WG");
     return !(e && e[0] == '0');
+}
+
+// f11's layout: the target's grid and the partial rows [nchunks][INFO_NSUM]
+struct InfoBufs {
+    GridBufs grid;
+    double *part;
+};
+static void bind_info(Carve &c, int Ns, int Nt, InfoBufs &I) {
+    bind_grid(c, Nt, I.grid);
+    I.part = c.take<double>(icp_chunks(Ns) * INFO_NSUM);
 }
 
 }  // namespace pdsc
@@ -349,6 +442,37 @@ int32_t pdsc_icp_point_to_point(const float *source, int32_t Ns, const float *ta
                                max_iteration, relative_fitness, relative_rmse, result, trans_f32);
         }
     }
+    HIPCHK(hipGetLastError());
+    return grid_status(G, s);
+}
+
+size_t pdsc_information_matrix_workspace_bytes(int32_t Ns, int32_t Nt) {
+    if (Ns < 1 || Nt < 1) return 0;
+    Carve c(nullptr);
+    InfoBufs I;
+    bind_info(c, Ns, Nt, I);
+    return c.off;
+}
+
+// Builds the target's grid (cell = max_distance, as f5), one lane per source point, one finishing wave.
+int32_t pdsc_information_matrix(const float *source, int32_t Ns, const float *target, int32_t Nt, const double *trans,
+                                double max_distance, pdsc_information_result *result, int32_t *corr, void *ws,
+                                size_t ws_bytes, pdsc_stream_t stream) {
+    if (Ns < 1 || Nt < 1) return fail(PDSC_ERR_ARG, "Ns=%d Nt=%d (need >= 1)", Ns, Nt);
+    if (!(max_distance > 0.0) || !std::isfinite(max_distance))
+        return fail(PDSC_ERR_ARG, "max_distance %g must be > 0 and finite", max_distance);
+    if (!source || !target || !result || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_information_matrix_workspace_bytes(Ns, Nt)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    InfoBufs I;
+    bind_info(c, Ns, Nt, I);
+    const GridBufs &G = I.grid;
+    HIPCHK(build_grid(target, Nt, max_distance, 0.0, G, s));
+    const int nchunks = (int)icp_chunks(Ns);
+    hipLaunchKernelGGL(info_eval_kernel, dim3(nchunks), dim3(ICP_CHUNK), 0, s, source, Ns, target, G.st, max_distance,
+                       max_distance * max_distance, G.view, trans, nchunks, I.part, corr);
+    hipLaunchKernelGGL(info_finish_kernel, dim3(1), dim3(64), 0, s, I.part, nchunks, result);
     HIPCHK(hipGetLastError());
     return grid_status(G, s);
 }
