@@ -370,7 +370,10 @@ int32_t pdsc_build_correspondences(const float *src_desc, const float *tgt_desc,
  * and capacity errors found on the device).
  *
  * pdsc_ply_read_xyz (HOST memory, o3d.io.read_point_cloud): the vertex x, y, z
- * of a binary_little_endian or ascii PLY.  xyz == NULL: only *n_points.     */
+ * of a binary_little_endian or ascii PLY.  xyz == NULL: only *n_points.  An
+ * element count the file cannot back (negative, or more rows than the bytes
+ * after the header hold) is PDSC_ERR_ARG, from the size query already; a zero
+ * vertex count is an empty cloud (*n_points = 0).                            */
 int32_t pdsc_ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t *n_points);
 /* KDTreeSearchParamHybrid(radius, max_nn) for every point of the cloud: nbr
  * [n,max_nn] (ascending (d^2, index), the point itself first, -1 padded),

@@ -155,7 +155,23 @@ def estimate_normals(pts, radius, max_nn=30, viewpoint=None, queries=None, orien
     qidx = np.arange(len(cloud)) if queries is None else np.asarray(queries, np.int64)
     nbr, _, cnt = radius_knn(cloud, radius, max_nn, queries=qidx)
     p = cloud[qidx]
-    n = len(p)
+    C = neighbourhood_covariance(cloud, nbr, cnt)
+    w = np.linalg.eigvalsh(C)
+    nv = fast_eigen3x3(C)
+    zero = (cnt < 3) | np.all(nv == 0, 1)
+    nv[zero] = (0.0, 0.0, 1.0)
+    if orient != "open3d":
+        vp = cloud.astype(np.float64).mean(0) if orient == "centroid" else np.asarray(viewpoint, np.float64)
+        flip = np.sum(nv * (vp - p.astype(np.float64)), 1) < 0
+        nv[flip] *= -1
+    return nv.astype(np.float32), w
+
+
+def neighbourhood_covariance(cloud, nbr, cnt):
+    """open3d ComputeNormal's covariance [q,3,3] of the neighbour lists: the fp64
+    cumulants of (x, y, z, xx, xy, xz, yy, yz, zz) summed in neighbour order, / k."""
+    cloud = np.asarray(cloud, np.float32)
+    n, max_nn = nbr.shape
     s = np.zeros((n, 9), np.float64)
     for t in range(int(max_nn)):
         m = cnt > t
@@ -171,19 +187,12 @@ def estimate_normals(pts, radius, max_nn=30, viewpoint=None, queries=None, orien
     C[:, 0, 1] = C[:, 1, 0] = s[:, 4] - s[:, 0] * s[:, 1]
     C[:, 0, 2] = C[:, 2, 0] = s[:, 5] - s[:, 0] * s[:, 2]
     C[:, 1, 2] = C[:, 2, 1] = s[:, 7] - s[:, 1] * s[:, 2]
-    w = np.linalg.eigvalsh(C)
-    nv = fast_eigen3x3(C)
-    zero = (cnt < 3) | np.all(nv == 0, 1)
-    nv[zero] = (0.0, 0.0, 1.0)
-    if orient != "open3d":
-        vp = cloud.astype(np.float64).mean(0) if orient == "centroid" else np.asarray(viewpoint, np.float64)
-        flip = np.sum(nv * (vp - p.astype(np.float64)), 1) < 0
-        nv[flip] *= -1
-    return nv.astype(np.float32), w
+    return C
 
 
-def pair_features(p1, n1, p2, n2):
-    """open3d ComputePairFeatures (PCL computePairFeatures), vectorised: (f0, f1, f2)."""
+def pair_features(p1, n1, p2, n2, detail=False):
+    """open3d ComputePairFeatures (PCL computePairFeatures), vectorised: (f0, f1, f2);
+    with `detail` also the values its branches test: (angle1, angle2, f3, vn)."""
     dp = p2 - p1
     f3 = np.sqrt(dp[:, 0] * dp[:, 0] + dp[:, 1] * dp[:, 1] + dp[:, 2] * dp[:, 2])
     ok = f3 != 0
@@ -207,7 +216,8 @@ def pair_features(p1, n1, p2, n2):
     f1 = dot(v, b)
     f0 = np.arctan2(dot(w, b), dot(a, b))
     z = np.zeros_like(f0)
-    return np.where(ok, f0, z), np.where(ok, f1, z), np.where(ok, theta, z)
+    f = np.where(ok, f0, z), np.where(ok, f1, z), np.where(ok, theta, z)
+    return f + (a1, a2, f3, vn) if detail else f
 
 
 def _bin(x):

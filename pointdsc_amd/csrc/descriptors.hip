@@ -714,7 +714,29 @@ static int ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t 
         err = "unsupported PLY format " + format;
         return 1;
     }
+    // the bytes after the header bound every element count (a count the file cannot hold is
+    // refused here, before a caller sizes a buffer by it)
+    const long body = ftell(f);
+    long end = -1;
+    if (body >= 0 && fseek(f, 0, SEEK_END) == 0) end = ftell(f);
+    if (body < 0 || end < body || fseek(f, body, SEEK_SET) != 0) {
+        fclose(f);
+        err = "cannot seek";
+        return 1;
+    }
+    // binary: rows of exactly `row` bytes.  ascii: a row takes at least a digit and a separator per
+    // property, or its newline alone without properties; only the file's last separator may be missing
+    auto fits = [&](int64_t count, size_t props, size_t row) {
+        const uint64_t left = (uint64_t)(end - ftell(f));
+        if (ascii) return (uint64_t)count <= (left + 1) / std::max<size_t>(1, 2 * props);
+        return row == 0 || (uint64_t)count <= left / row;
+    };
     for (const Elem &el : elems) {
+        if (el.count < 0) {
+            fclose(f);
+            err = "element '" + el.name + "' has a negative count";
+            return 1;
+        }
         if (el.name != "vertex") {  // skip a preceding element (fixed-size rows only)
             size_t row = 0;
             for (const Prop &p : el.props) {
@@ -725,10 +747,15 @@ static int ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t 
                 }
                 row += ply_type_size(p.type);
             }
+            if (!fits(el.count, el.props.size(), row)) {
+                fclose(f);
+                err = "truncated file: element '" + el.name + "' does not fit";
+                return 1;
+            }
             if (ascii) {
                 for (int64_t r = 0; r < el.count; ++r)
                     if (!fgets(line, sizeof line, f)) break;
-            } else if (fseek(f, (long)(row * el.count), SEEK_CUR) != 0) {
+            } else if (fseek(f, (long)(row * (size_t)el.count), SEEK_CUR) != 0) {
                 fclose(f);
                 err = "truncated file";
                 return 1;
@@ -754,6 +781,11 @@ static int ply_read_xyz(const char *path, float *xyz, int64_t capacity, int64_t 
         if (ix < 0 || iy < 0 || iz < 0) {
             fclose(f);
             err = "vertex element has no x/y/z";
+            return 1;
+        }
+        if (!fits(el.count, el.props.size(), row)) {
+            fclose(f);
+            err = ascii ? "truncated ascii vertex data" : "truncated binary vertex data";
             return 1;
         }
         *n_out = el.count;

@@ -61,6 +61,55 @@ def test_ply_variants(tmp_path):
         read_ply(str(tmp_path / "missing.ply"))
 
 
+_HDR = "ply\nformat {fmt} 1.0\n{pre}element vertex {n}\nproperty float x\nproperty float y\nproperty float z\nend_header\n"
+
+
+def test_ply_header_edges(tmp_path):
+    """Vertex counts the data cannot back -- negative, or larger than the file -- come back
+    as the library's argument error in both formats, from the size query already (so no
+    caller sizes a buffer by them); a zero count is an empty cloud; CRLF headers read."""
+    from pointdsc_amd.descriptors import read_ply
+    xyz = np.random.RandomState(1).randn(5, 3).astype(np.float32)
+    rows = "".join(f"{x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in xyz)
+
+    def write(name, fmt, n, body, pre="", crlf=False):
+        h = _HDR.format(fmt=fmt, n=n, pre=pre)
+        if crlf:
+            h, body = h.replace("\n", "\r\n"), body.replace(b"\n", b"\r\n") if fmt == "ascii" else body
+        (tmp_path / name).write_bytes(h.encode() + body)
+        return str(tmp_path / name)
+
+    for fmt, body in (("ascii", rows.encode()), ("binary_little_endian", xyz.tobytes())):
+        assert np.array_equal(read_ply(write("ok.ply", fmt, 5, body)), xyz)
+        assert np.array_equal(read_ply(write("crlf.ply", fmt, 5, body, crlf=True)), xyz)
+        assert np.array_equal(read_ply(write("short.ply", fmt, 4, body)), xyz[:4])  # trailing data is ignored
+        assert read_ply(write("zero.ply", fmt, 0, b"")).shape == (0, 3)
+        with pytest.raises(RuntimeError, match="negative count"):
+            read_ply(write("neg.ply", fmt, -5, body))
+        for n in (6, 1 << 40):  # one more than the data holds; far more than memory holds
+            with pytest.raises(RuntimeError, match="truncated"):
+                read_ply(write("long.ply", fmt, n, body))
+        pre = "element camera {}\nproperty float fx\n"
+        cam = b"1.5\n" if fmt == "ascii" else np.float32(1.5).tobytes()
+        assert np.array_equal(read_ply(write("pre.ply", fmt, 5, cam + body, pre=pre.format(1))), xyz)
+        with pytest.raises(RuntimeError, match="negative count"):
+            read_ply(write("preneg.ply", fmt, 5, cam + body, pre=pre.format(-1)))
+        with pytest.raises(RuntimeError, match="truncated"):
+            read_ply(write("prelong.ply", fmt, 5, cam + body, pre=pre.format(1 << 40)))
+    # the last ascii row without its newline still counts
+    assert np.array_equal(read_ply(write("nonl.ply", "ascii", 5, rows.encode().rstrip(b"\n"))), xyz)
+    # ... but binary rows have no separator to lose: one byte short is refused by the size query
+    import ctypes
+    from pointdsc_amd._call import call
+    path = write("byte.ply", "binary_little_endian", 5, xyz.tobytes()[:-1])
+    with pytest.raises(RuntimeError, match="truncated"):
+        call("pdsc_ply_read_xyz", path.encode(), None, 0, ctypes.c_int64(), device=None)
+    # an ascii element without properties before the vertices is skipped line by line
+    pre = "element marker 2\n"
+    assert np.array_equal(read_ply(write("bare.ply", "ascii", 5, b"\n\n" + rows.encode(), pre=pre)), xyz)
+    assert np.array_equal(read_ply(write("bare.ply", "binary_little_endian", 5, xyz.tobytes(), pre=pre)), xyz)
+
+
 def _rigid(seed):
     rng = np.random.RandomState(seed)
     q = rng.randn(4)
