@@ -1,8 +1,7 @@
 // api.hip -- the forward: the testing and training forwards of include/pdsc.h,
-// the a-row stage entries that share their helpers (compat, encoder, attention,
-// seeds, seed kNN, NSM, rigid transform, hypotheses, refinement), weight
-// packing, and the plan, timing and diag queries.  Nothing else: every other
-// row's entry points live in the row's file (abi.hpp).
+// the encoder and attention entries that share their helpers (Dims, EncBufs),
+// weight packing, and the plan, timing and diag queries.  Nothing else: every
+// other row's entry points live in the row's file (abi.hpp).
 //
 // Host-side orchestration only: argument checks, workspace carving and kernel
 // launches on the caller's stream.  No allocation, no synchronisation.
@@ -311,37 +310,6 @@ static int run_encoder_fwd(const PackLayout &lay, const float *packed, const flo
     return r;
 }
 
-struct NsmBufs {
-    float *hist, *weights;
-    _Float16 *ns;  // split normed copy (standalone API only; the forward passes pw_last's)
-    unsigned *mask;
-};
-
-NsmBufs carve_nsm(Carve &c, int B, int N, int S, int k, int T, bool own_split) {
-    NsmBufs n;
-    n.ns = own_split ? c.take<_Float16>((size_t)B * N * 2 * CH) : nullptr;
-    n.hist = c.take<float>((size_t)B * S * std::max(T, 1) * k);
-    n.mask = c.take<unsigned>((size_t)B * S);  // per-seed allclose bits
-    n.weights = c.take<float>((size_t)B * S * k);
-    return n;
-}
-
-// normed_s: the split normed copy, or NULL to build it here from normed (H3);
-// f32: the Gram reads normed itself
-int run_nsm(const TailPlan &tp, const float *normed, const _Float16 *normed_s, bool f32, const float *src,
-            const float *tgt, const int *knn, int B, int N, int S, int k, int T, const float *sigma, const float *sigma_d,
-            const NsmBufs &nb, float *weights, int *iters, bool batch_global, hipStream_t s, Ragged rg = {}) {
-    if (!f32 && !normed_s) {
-        HIPCHK(launch_split_rows(normed, (size_t)B * N, nb.ns, s));
-        normed_s = nb.ns;
-    }
-    const void *feats = f32 ? static_cast<const void *>(normed) : static_cast<const void *>(normed_s);
-    if (T > 0)
-        HIPCHK(launch_nsm_seed(tp, feats, f32, src, tgt, knn, B, N, S, k, T, sigma, sigma_d, nb.hist, nb.mask, s, rg));
-    HIPCHK(launch_nsm_finish(nb.hist, nb.mask, B, S, k, T, batch_global, weights, iters, s, rg));
-    return PDSC_OK;
-}
-
 struct FwdBufs {
     int *range;  // [B] the fp16 range guard's per-pair flags: the workspace's first bytes (pdsc_range_status)
     float *M, *normed, *conf, *lm, *kdist, *seed_trans, *weights, *hsums;
@@ -365,7 +333,7 @@ FwdBufs carve_forward(Carve &c, const Dims &d) {
     f.seeds = c.take<int>((size_t)d.B * d.S);
     f.kdist = c.take<float>((size_t)d.B * d.S * d.N);
     f.knn = c.take<int>((size_t)d.B * d.S * d.k);
-    f.nsm = carve_nsm(c, d.B, d.N, d.S, d.k, d.T, false);
+    f.nsm = carve_nsm(c, d.B, d.S, d.k, d.T);
     f.weights = f.nsm.weights;
     f.seed_trans = c.take<float>((size_t)d.B * d.S * 16);
     f.counts = c.take<int>((size_t)d.B * d.S);
@@ -470,25 +438,6 @@ int32_t pdsc_pack_weights(const pdsc_config *cfg, const float *const *P, float *
     HIPCHK(dense(lay.c2, t + 4, CLS, CLS, false));
     HIPCHK(launch_copy(P[t + 6], packed + lay.c4_w, CLS, s));
     HIPCHK(launch_copy(P[t + 7], packed + lay.c4_b, 1, s));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------------------------- a1
-int32_t pdsc_compat_f32(const float *src, const float *tgt, int32_t B, int32_t N,
-                        const float *sigma_d_dev, float *M, pdsc_stream_t stream) {
-    if (!src || !tgt || !sigma_d_dev || !M) return fail(PDSC_ERR_ARG, "null pointer");
-    if (B < 1 || N < 1) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    HIPCHK(launch_compat(src, tgt, B, N, sigma_d_dev, M, S_(stream)));
-    return PDSC_OK;
-}
-
-size_t pdsc_compat_packed_floats(int32_t N) { return N < 1 ? 0 : mpack_floats(N); }
-
-int32_t pdsc_compat_packed_f32(const float *src, const float *tgt, int32_t B, int32_t N,
-                               const float *sigma_d_dev, float *Mp, pdsc_stream_t stream) {
-    if (!src || !tgt || !sigma_d_dev || !Mp) return fail(PDSC_ERR_ARG, "null pointer");
-    if (B < 1 || N < 1) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    HIPCHK(launch_compat_packed(src, tgt, B, N, sigma_d_dev, Mp, S_(stream)));
     return PDSC_OK;
 }
 
@@ -634,143 +583,6 @@ int32_t pdsc_packed_block(const pdsc_config *cfg, int32_t layer, int32_t block, 
     const DenseOff d[8] = {lo.pcn, lo.fc0, lo.fc3, lo.fc6, lo.q, lo.k, lo.v, lo.vm};
     const DenseOff &o = d[block];
     offsets[0] = o.w, offsets[1] = o.bias, offsets[2] = o.alpha, offsets[3] = o.beta, offsets[4] = o.scale;
-    return PDSC_OK;
-}
-
-// -------------------------------------------------------------------- a5
-int32_t pdsc_pick_seeds(const float *src, const float *conf, int32_t B, int32_t N, float radius,
-                        int32_t S, int32_t *seeds, float *is_local_max, pdsc_stream_t stream) {
-    if (!src || !conf || !seeds || !is_local_max) return fail(PDSC_ERR_ARG, "null pointer (is_local_max is used as scratch)");
-    if (B < 1 || N < 1 || S < 1 || S > N) return fail(PDSC_ERR_ARG, "B=%d N=%d S=%d", B, N, S);
-    hipStream_t s = S_(stream);
-    const TailPlan tp = plan_tail(B, N, S);
-    HIPCHK(launch_local_max(tp, src, conf, B, N, radius, is_local_max, s));
-    HIPCHK(launch_seed_rank(tp, conf, is_local_max, B, N, S, seeds, s));
-    return PDSC_OK;
-}
-
-// -------------------------------------------------------------------- a6
-// a6 (:250-252) for the forwards: knn [B][S][k]; dist [B][S][N] scratch
-int run_seed_knn(const TailPlan &tp, const float *normed, const _Float16 *normed_s, bool f32, const int *seeds, int B,
-                 int N, int S, int k, float *dist, int *knn, hipStream_t s, Ragged rg = {}) {
-    // (no zero fill of knn: knn_select writes all k entries of every seed row it
-    // owns -- ranks 1 .. k of k + 1 distinct (key, index) candidates -- and the
-    // rows past a ragged pair's own seeds are never read; readers clamp indices)
-    if (f32) {
-        HIPCHK(launch_knn_dist_f32(normed, seeds, B, N, S, dist, s, rg));
-    } else {
-        HIPCHK(launch_knn_dist(normed_s, seeds, B, N, S, dist, s, rg));
-    }
-    HIPCHK(launch_knn_select(tp, dist, B, N, S, k, knn, s, rg));
-    return PDSC_OK;
-}
-
-// the seed rows' distances [B][S][N] and the split normed copy [B][N][2][CH]
-struct SeedKnnBufs {
-    float *dist;
-    _Float16 *ns;
-};
-static void bind_seed_knn(Carve &c, int B, int N, int S, SeedKnnBufs &W) {
-    W.dist = c.take<float>((size_t)B * S * N);
-    W.ns = c.take<_Float16>((size_t)B * N * 2 * CH);
-}
-
-size_t pdsc_seed_knn_workspace_bytes(int32_t B, int32_t N, int32_t S) {
-    Carve c(nullptr);
-    SeedKnnBufs W;
-    bind_seed_knn(c, B, N, S, W);
-    return c.off;
-}
-
-int32_t pdsc_seed_knn(const float *normed, const int32_t *seeds, int32_t B, int32_t N, int32_t C,
-                      int32_t S, int32_t k, int32_t precision, int32_t *knn, void *ws, size_t ws_bytes,
-                      pdsc_stream_t stream) {
-    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
-        return fail(PDSC_ERR_ARG, "precision=%d", precision);
-    if (C != CH) return fail(PDSC_ERR_UNSUPPORTED, "C=%d (only %d)", C, CH);
-    if (!normed || !seeds || !knn || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    if (B < 1 || S < 1 || k < 1 || k + 1 > N || k > 63) return fail(PDSC_ERR_ARG, "B=%d N=%d S=%d k=%d", B, N, S, k);
-    RET_IF(need_ws(ws_bytes, pdsc_seed_knn_workspace_bytes(B, N, S)));
-    hipStream_t s = S_(stream);
-    Carve c(ws);
-    SeedKnnBufs W;
-    bind_seed_knn(c, B, N, S, W);
-    const bool f32 = precision == PDSC_PRECISION_F32;
-    if (!f32) HIPCHK(launch_split_rows(normed, (size_t)B * N, W.ns, s));
-    return run_seed_knn(plan_tail(B, N, S), normed, W.ns, f32, seeds, B, N, S, k, W.dist, knn, s);
-}
-
-// ----------------------------------------------------------------- a7-a8
-size_t pdsc_nsm_workspace_bytes(int32_t B, int32_t N, int32_t S, int32_t k, int32_t T) {
-    Carve c(nullptr);
-    carve_nsm(c, B, N, S, k, T, true);
-    return c.off;
-}
-
-int32_t pdsc_nsm_weights(const float *normed, const float *src, const float *tgt, const int32_t *knn,
-                         int32_t B, int32_t N, int32_t C, int32_t S, int32_t k, int32_t T, int32_t precision,
-                         const float *sigma, const float *sigma_d, float *weights, int32_t *iters,
-                         void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    if (C != CH) return fail(PDSC_ERR_UNSUPPORTED, "C=%d (only %d)", C, CH);
-    if (!normed || !src || !tgt || !knn || !sigma || !sigma_d || !weights || !ws)
-        return fail(PDSC_ERR_ARG, "null pointer");
-    if (B < 1 || S < 1 || k < 1 || k > 63 || N < k + 1 || T < 0 || T > 31)
-        return fail(PDSC_ERR_ARG, "B=%d N=%d S=%d k=%d T=%d (1 <= k <= min(63, N-1), 0 <= T <= 31)", B, N, S, k, T);
-    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
-        return fail(PDSC_ERR_ARG, "precision=%d", precision);
-    RET_IF(need_ws(ws_bytes, pdsc_nsm_workspace_bytes(B, N, S, k, T)));
-    Carve c(ws);
-    NsmBufs nb = carve_nsm(c, B, N, S, k, T, true);
-    return run_nsm(plan_tail(B, N, S), normed, nullptr, precision == PDSC_PRECISION_F32, src, tgt, knn, B, N, S, k, T,
-                   sigma, sigma_d, nb, weights, iters, true, S_(stream));
-}
-
-// -------------------------------------------------------------------- a9
-int32_t pdsc_rigid_transform_3d(const float *A, const float *Bp, const float *w, int32_t nb, int32_t n,
-                                float *trans, pdsc_stream_t stream) {
-    if (!A || !Bp || !trans) return fail(PDSC_ERR_ARG, "null pointer");
-    if (nb < 1 || n < 0) return fail(PDSC_ERR_ARG, "nb=%d n=%d", nb, n);
-    HIPCHK(launch_rigid(A, Bp, w, nb, n, trans, S_(stream)));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------------------------- a10
-static float *bind_hypothesis_sums(Carve &c, int B, int S) { return c.take<float>((size_t)B * S * 15); }
-
-size_t pdsc_seed_hypotheses_workspace_bytes(int32_t B, int32_t S) {
-    Carve c(nullptr);
-    bind_hypothesis_sums(c, B, S);
-    return c.off;
-}
-
-int32_t pdsc_seed_hypotheses(const float *src, const float *tgt, const int32_t *knn, const float *weights,
-                             int32_t B, int32_t N, int32_t S, int32_t k, float tau, float *seed_trans,
-                             float *fitness, int32_t *best, float *trans, float *labels, void *ws,
-                             size_t ws_bytes, pdsc_stream_t stream) {
-    if (!src || !tgt || !knn || !weights || !trans || !labels || !seed_trans)
-        return fail(PDSC_ERR_ARG, "null pointer (seed_trans is required as scratch)");
-    if (B < 1 || S < 1 || k < 1 || k > 63 || N < k + 1)
-        return fail(PDSC_ERR_ARG, "B=%d N=%d S=%d k=%d (1 <= k <= min(63, N-1))", B, N, S, k);
-    hipStream_t s = S_(stream);
-    // the integer inlier counts live in the caller's fitness buffer until select_best turns
-    // each into count / N (same thread, same element)
-    if (!fitness) return fail(PDSC_ERR_ARG, "fitness [B,S] buffer is required (hosts the inlier counts)");
-    int *counts = reinterpret_cast<int *>(fitness);
-    if (!ws || ws_bytes < pdsc_seed_hypotheses_workspace_bytes(B, S))
-        return fail(PDSC_ERR_ARG, "workspace too small");
-    Carve c(ws);
-    HIPCHK(launch_hypotheses(plan_tail(B, N, S), src, tgt, knn, weights, B, N, S, k, tau, seed_trans, counts,
-                             bind_hypothesis_sums(c, B, S), s));
-    HIPCHK(launch_select_best(src, tgt, seed_trans, counts, B, N, S, tau, fitness, best, trans, labels, s));
-    return PDSC_OK;
-}
-
-// ------------------------------------------------------------------- a11
-int32_t pdsc_post_refine(float *trans, const float *src, const float *tgt, int32_t B, int32_t N, float thr,
-                         pdsc_stream_t stream) {
-    if (!trans || !src || !tgt) return fail(PDSC_ERR_ARG, "null pointer");
-    if (B < 1 || N < 1) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    HIPCHK(launch_post_refine(trans, src, tgt, B, N, thr, S_(stream)));
     return PDSC_OK;
 }
 

@@ -15,6 +15,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "abi.hpp"
 #include "pdsc_internal.hpp"
 
 namespace pdsc {
@@ -375,3 +376,27 @@ hipError_t launch_ragged_order(const int32_t *counts, int B, int *po, hipStream_
 }
 
 }  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+int32_t pdsc_compat_f32(const float *src, const float *tgt, int32_t B, int32_t N,
+                        const float *sigma_d_dev, float *M, pdsc_stream_t stream) {
+    if (!src || !tgt || !sigma_d_dev || !M) return fail(PDSC_ERR_ARG, "null pointer");
+    if (B < 1 || N < 1) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
+    HIPCHK(launch_compat(src, tgt, B, N, sigma_d_dev, M, S_(stream)));
+    return PDSC_OK;
+}
+
+size_t pdsc_compat_packed_floats(int32_t N) { return N < 1 ? 0 : mpack_floats(N); }
+
+int32_t pdsc_compat_packed_f32(const float *src, const float *tgt, int32_t B, int32_t N,
+                               const float *sigma_d_dev, float *Mp, pdsc_stream_t stream) {
+    if (!src || !tgt || !sigma_d_dev || !Mp) return fail(PDSC_ERR_ARG, "null pointer");
+    if (B < 1 || N < 1) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
+    HIPCHK(launch_compat_packed(src, tgt, B, N, sigma_d_dev, Mp, S_(stream)));
+    return PDSC_OK;
+}
+
+}  // extern "C"

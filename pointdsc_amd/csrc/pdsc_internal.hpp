@@ -255,22 +255,21 @@ hipError_t launch_local_max(const TailPlan &tp, const float *src, const float *c
 hipError_t launch_seed_rank(const TailPlan &tp, const float *conf, const float *lm, int B, int N, int S, int *seeds,
                             hipStream_t s, Ragged rg = {}, uint32_t *scratch = nullptr);
 
-// ns: normed as [B][N][2][128] fp16 hi/lo (qk_pos order, attention_h3.hpp)
-hipError_t launch_knn_dist(const _Float16 *ns, const int *seeds, int B, int N, int S, float *dist,
-                           hipStream_t s, Ragged rg = {});
+// normed_s (unused when f32): normed as [rows][2][128] fp16 hi/lo in qk_pos order; feats: normed_s, or normed when f32
 hipError_t launch_split_rows(const float *x, size_t rows, _Float16 *out, hipStream_t s);
-// PDSC_PRECISION_F32 seed-row distances from the fp32 normed rows [B][N][128]
-hipError_t launch_knn_dist_f32(const float *normed, const int *seeds, int B, int N, int S, float *dist,
-                               hipStream_t s, Ragged rg = {});
-hipError_t launch_knn_select(const TailPlan &tp, const float *dist, int B, int N, int S, int k, int *knn,
-                             hipStream_t s, Ragged rg = {});
-// feats: the split normed copy [B][N][2][128] fp16 (as launch_knn_dist reads it),
-// or the fp32 normed rows [B][N][128] when f32
+int run_seed_knn(const TailPlan &tp, const float *normed, const _Float16 *normed_s, bool f32, const int *seeds, int B,
+                 int N, int S, int k, float *dist, int *knn, hipStream_t s, Ragged rg = {});
 hipError_t launch_nsm_seed(const TailPlan &tp, const void *feats, bool f32, const float *src, const float *tgt,
                            const int *knn, int B, int N, int S, int k, int T, const float *sigma, const float *sigma_d,
                            float *hist, unsigned *seed_flags, hipStream_t s, Ragged rg = {});
-hipError_t launch_nsm_finish(const float *hist, const unsigned *seed_flags, int B, int S, int k, int T, bool batch_global,
-                             float *weights, int *iters_used, hipStream_t s, Ragged rg = {});
+struct NsmBufs {  // a7-a8 (nsm.hip): the iterates [B][S][max(T, 1)][k], per-seed allclose bits, weights [B][S][k]
+    float *hist, *weights;
+    unsigned *mask;
+};
+NsmBufs carve_nsm(Carve &c, int B, int S, int k, int T);
+int run_nsm(const TailPlan &tp, const float *normed, const _Float16 *normed_s, bool f32, const float *src,
+            const float *tgt, const int *knn, int B, int N, int S, int k, int T, const float *sigma, const float *sigma_d,
+            const NsmBufs &nb, float *weights, int *iters, bool batch_global, hipStream_t s, Ragged rg = {});
 // sums: scratch [B][S][15]
 // hist != NULL (the testing forward): the NSM weights are finished inside the
 // first launch (nsm_finish's arithmetic, per-pair allclose over hist /

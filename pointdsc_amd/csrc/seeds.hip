@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "abi.hpp"
 #include "launch_plan.hpp"
 #include "pdsc_internal.hpp"
 
@@ -649,3 +650,20 @@ hipError_t launch_seed_rank(const TailPlan &tp, const float *conf, const float *
 }
 
 }  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+int32_t pdsc_pick_seeds(const float *src, const float *conf, int32_t B, int32_t N, float radius,
+                        int32_t S, int32_t *seeds, float *is_local_max, pdsc_stream_t stream) {
+    if (!src || !conf || !seeds || !is_local_max) return fail(PDSC_ERR_ARG, "null pointer (is_local_max is used as scratch)");
+    if (B < 1 || N < 1 || S < 1 || S > N) return fail(PDSC_ERR_ARG, "B=%d N=%d S=%d", B, N, S);
+    hipStream_t s = S_(stream);
+    const TailPlan tp = plan_tail(B, N, S);
+    HIPCHK(launch_local_max(tp, src, conf, B, N, radius, is_local_max, s));
+    HIPCHK(launch_seed_rank(tp, conf, is_local_max, B, N, S, seeds, s));
+    return PDSC_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 """Exact references, case tables and input builders for the forward's front half:
 a1 compat (compat.hip), a5 seeds (seeds.hip), a6 seed kNN (knn_dist* / knn_select
-of nsm.hip) and f1 correspondences (corr.hip) -- the index, mask and bit-exact
+of knn.hip) and f1 correspondences (corr.hip) -- the index, mask and bit-exact
 stages.  tests/test_gpu_front_stages.py runs the cases on the GPU;
 tests/test_front_reference.py proves on the CPU that the references and the cases
 are what they claim, so a bad seed or a misread path fails there.
@@ -8,7 +8,7 @@ are what they claim, so a bad seed or a misread path fails there.
 numpy only (no torch device code).  The truth is the oracle (oracle/pdsc_oracle.py,
 pinned to the reference's goldens) for everything bit-exact, and fp64 evaluated on
 the fp32 inputs for the kNN distances.  Which kernel form a shape reaches is read
-from the launchers (seeds.hip plan_tail, nsm.hip launch_knn_dist /
+from the launchers (seeds.hip plan_tail, knn.hip launch_knn_dist /
 launch_knn_select, compat.hip) and restated beside each table."""
 import functools
 
@@ -287,7 +287,7 @@ def isolation_case():
 
 
 # =================================================================== a6 seed kNN
-KNN_EPS = 2e-6  # conftest.assert_knn_equivalent's bar: the H3 distance error is <= 2^-21 (nsm.hip)
+KNN_EPS = 2e-6  # conftest.assert_knn_equivalent's bar: the H3 distance error is <= 2^-21 (knn.hip)
 C = 128
 
 
@@ -299,7 +299,7 @@ def _k(**kw):
     return kw
 
 
-# Paths (nsm.hip): knn_select_kernel<R>, R = 16 ceil(N / 1024) up to N = 8192, then
+# Paths (knn.hip): knn_select_kernel<R>, R = 16 ceil(N / 1024) up to N = 8192, then
 # the memory form <0>.  In <R > 0> lane l owns keys 256 i + 4 l + e, so N <= 4 (k + 1)
 # leaves fewer than k + 1 lanes with a key: tau0 is all-ones and every key qualifies
 # (c = N): bitonic ranking to N = 64, readlane ranking to 128, register radix select
@@ -330,7 +330,7 @@ KNN_CASES = (
 
 
 def knn_wg5(B, N, S):
-    """launch_knn_dist's rule (nsm.hip): workgroups at 5 key tiles each."""
+    """launch_knn_dist's rule (knn.hip): workgroups at 5 key tiles each."""
     nkt = (N + 31) // 32
     return ((nkt + 4) // 5) * ((S + 127) // 128) * B
 

@@ -1,4 +1,5 @@
-"""The argument checks of every f-row entry point, replayed against a recorded
+"""The argument checks of every f-row entry point and of the a-row stage entries
+that take only pointers and scalars, replayed against a recorded
 table (tests/golden/abi_errors/abi_errors.json) -- no GPU needed: every call
 here is rejected on the host before the entry's first HIP call.
 
@@ -166,6 +167,49 @@ ENTRIES = {
          {15: short("pdsc_gc_ransac_workspace_bytes", 100)}],
         [{2: 2, 6: 0}, {6: 0, 3: 0.0}, {4: 1.5, 7: 0.0}, {7: 1.5, 5: 1025}, {5: 0, 0: None},
          {1: None, 15: short("pdsc_gc_ransac_workspace_bytes", 100)}]),
+    # a1 (compat.hip)
+    "pdsc_compat_f32": (
+        [P, P, 2, 10, P, P, None],
+        [{0: None}, {4: None}, {5: None}, {2: 0}, {3: 0}],
+        [{1: None, 2: 0}, {5: None, 3: 0}]),
+    "pdsc_compat_packed_f32": (
+        [P, P, 2, 10, P, P, None],
+        [{0: None}, {4: None}, {5: None}, {2: 0}, {3: 0}],
+        [{1: None, 2: 0}, {5: None, 3: 0}]),
+    # a5 (seeds.hip)
+    "pdsc_pick_seeds": (
+        [P, P, 2, 100, 0.1, 10, P, P, None],
+        [{0: None}, {1: None}, {6: None}, {7: None}, {2: 0}, {3: 0}, {5: 0}, {5: 101}],
+        [{6: None, 5: 0}, {1: None, 2: 0}]),
+    # a6 (knn.hip)
+    "pdsc_seed_knn": (
+        [P, P, 2, 100, 128, 10, 8, 0, P, P, BIG, None],
+        [{7: 2}, {7: -1}, {4: 64}, {0: None}, {1: None}, {8: None}, {9: None}, {2: 0}, {5: 0}, {6: 0}, {6: 100}, {6: 64},
+         {10: short("pdsc_seed_knn_workspace_bytes", 2, 100, 10)}],
+        [{7: 2, 4: 64}, {4: 64, 0: None}, {1: None, 2: 0}, {6: 64, 10: short("pdsc_seed_knn_workspace_bytes", 2, 100, 10)}]),
+    # a7-a8 (nsm.hip)
+    "pdsc_nsm_weights": (
+        [P, P, P, P, 2, 100, 128, 10, 8, 10, 0, P, P, P, None, P, BIG, None],
+        [{6: 64}, {0: None}, {1: None}, {2: None}, {3: None}, {11: None}, {12: None}, {13: None}, {15: None}, {4: 0},
+         {7: 0}, {8: 0}, {8: 64}, {5: 8}, {9: -1}, {9: 32}, {10: 2},
+         {16: short("pdsc_nsm_workspace_bytes", 2, 100, 10, 8, 10)}],
+        [{6: 64, 0: None}, {1: None, 4: 0}, {9: 32, 10: 2},
+         {10: 2, 16: short("pdsc_nsm_workspace_bytes", 2, 100, 10, 8, 10)}]),
+    # a9-a11 (hypotheses.hip)
+    "pdsc_rigid_transform_3d": (
+        [P, P, None, 2, 10, P, None],
+        [{0: None}, {1: None}, {5: None}, {3: 0}, {4: -1}],
+        [{0: None, 3: 0}, {5: None, 4: -1}]),
+    "pdsc_seed_hypotheses": (
+        [P, P, P, P, 2, 100, 10, 8, 0.1, P, P, None, P, P, P, BIG, None],
+        [{0: None}, {1: None}, {2: None}, {3: None}, {9: None}, {12: None}, {13: None}, {4: 0}, {6: 0}, {7: 0}, {7: 64},
+         {5: 8}, {10: None}, {14: None}, {15: short("pdsc_seed_hypotheses_workspace_bytes", 2, 10)}],
+        [{2: None, 4: 0}, {7: 64, 10: None}, {10: None, 14: None},
+         {10: None, 15: short("pdsc_seed_hypotheses_workspace_bytes", 2, 10)}]),
+    "pdsc_post_refine": (
+        [P, P, P, 2, 100, 0.1, None],
+        [{0: None}, {1: None}, {2: None}, {3: 0}, {4: 0}],
+        [{1: None, 3: 0}, {0: None, 4: 0}]),
 }
 
 

@@ -1,7 +1,7 @@
 """The forward's front half on the GPU against the exact references of
 tests/front_reference.py (run with -m gpu): pdsc_compat_f32 / pdsc_compat_packed_f32
 (a1), pdsc_pick_seeds (a5), pdsc_seed_knn (a6) and pdsc_mutual_nn /
-pdsc_build_correspondences (f1) at the shapes where compat.hip, seeds.hip, nsm.hip's
+pdsc_build_correspondences (f1) at the shapes where compat.hip, seeds.hip, knn.hip's
 knn kernels and corr.hip take another path.  Everything goes through the C ABI
 (pointdsc_amd._lib) on output buffers prefilled with a sentinel, so an unwritten slot
 shows; every form is reached by shape under the default knobs, and where

@@ -1,6 +1,6 @@
 """pdsc_nsm_weights, pdsc_seed_hypotheses, pdsc_post_refine and
 pdsc_rigid_transform_3d against the fp64 reference of tests/nsm_reference.py at the
-shapes where nsm.hip takes another path: every KC variant of nsm_seed_kernel and
+shapes where nsm.hip or hypotheses.hip takes another path: every KC variant of nsm_seed_kernel and
 the edges of its Gram tiles, T = 0 / 1 / 31, the four (seed_wpb, kabsch_small)
 launch plans, a partial count_inliers group, S > 256 in the argmax, exact ties at
 the inlier threshold and between seeds, and several pairs per post_refine launch

@@ -130,7 +130,7 @@ def test_nsm_case_preconditions(c):
 def test_hypotheses_case_preconditions(c):
     d = R.hyp_case(c)
     B, N, S, k = (c[n] for n in "BNSk")
-    # the launch plan the shape selects (nsm.hip: seed_wpb, kabsch_small, HS = 8)
+    # the launch plan the shape selects (hypotheses.hip: seed_wpb, kabsch_small, HS = 8)
     plan = (1 if B * ((S + 3) // 4) < 512 else 4, B * S <= 1024)
     want = {"B1-N200-S20-k40": (1, True), "B3-N257-S600-k8": (1, False), "B512-N16-S1-k8": (4, True),
             "B8-N300-S300-k17": (4, False)}

@@ -37,11 +37,11 @@ def one(N):
     torch.cuda.synchronize()
     reps = []
     for _ in range(5):
-        assert L.pdsc_diag_nsm_stamps_clear() == 0
+        assert L.pdsc_diag_refine_stamps_clear() == 0
         plan.run(c, s, t)
         torch.cuda.synchronize()
         buf = np.zeros(ST_WGS * 4 * ST_PER_WAVE, np.uint64)
-        assert L.pdsc_diag_nsm_stamps(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
+        assert L.pdsc_diag_refine_stamps(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
         st = buf.reshape(ST_WGS * 4, ST_PER_WAVE)[-1].astype(np.int64)
         its = int(st[98])
         us = lambda a, b: float(st[b] - st[a]) / 100.0
