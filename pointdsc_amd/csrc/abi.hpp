@@ -16,6 +16,12 @@ namespace pdsc {
 // (api.hip: the one definition, beside the string it writes).
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// The checks the forwards and the encoder row's entries share (api.hip): the
+// config's supported ranges; then B, N and what the config makes of N: the seeds
+// S = int(N * ratio) and k = min(cfg k, N - 1), the one place that computes them.
+int check_cfg(const pdsc_config *cfg);
+int check_shape(const pdsc_config *cfg, int B, int N, int &S, int &k);
+
 inline hipStream_t S_(pdsc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int need_ws(size_t have, size_t need) {

@@ -1,7 +1,7 @@
-// api.hip -- the forward: the testing and training forwards of include/pdsc.h,
-// the encoder and attention entries that share their helpers (Dims, EncBufs),
-// weight packing, and the plan, timing and diag queries.  Nothing else: every
-// other row's entry points live in the row's file (abi.hpp).
+// api.hip -- the forward: the testing and training forwards of include/pdsc.h
+// with their timing, range and launch-plan queries, and the error convention
+// every entry shares (fail, check_cfg, check_shape).  Nothing else: every row's
+// entry points live in the row's file (abi.hpp).
 //
 // Host-side orchestration only: argument checks, workspace carving and kernel
 // launches on the caller's stream.  No allocation, no synchronisation.
@@ -10,11 +10,11 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "abi.hpp"
+#include "encoder.hpp"
 #include "launch_plan.hpp"
 #include "pdsc_internal.hpp"
 
@@ -22,11 +22,9 @@ using namespace pdsc;
 
 namespace {
 thread_local std::string g_err;  // pdsc_last_error
-thread_local std::string g_name;
 }  // namespace
 
 namespace pdsc {
-thread_local int g_diag_qkv_delay = 0;  // pdsc_diag_qkv_delay (tests only)
 
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -37,18 +35,6 @@ int fail(int code, const char *fmt, ...) {
     g_err = buf;
     return code;
 }
-}  // namespace pdsc
-
-namespace {
-
-// measurement hook (pdsc_attention_timing): events recorded around attention launches
-thread_local hipEvent_t *g_tstart = nullptr, *g_tstop = nullptr;
-thread_local int g_tcap = 0;
-thread_local int32_t *g_tcount = nullptr;
-// pdsc_forward_timing: PDSC_FORWARD_STAGES + 1 events per forward call
-thread_local hipEvent_t *g_fev = nullptr;
-thread_local int g_fcap = 0;
-thread_local int32_t *g_fcount = nullptr;
 
 int check_cfg(const pdsc_config *cfg) {
     if (!cfg) return fail(PDSC_ERR_ARG, "cfg is NULL");
@@ -65,6 +51,24 @@ int check_cfg(const pdsc_config *cfg) {
     return PDSC_OK;
 }
 
+int check_shape(const pdsc_config *cfg, int B, int N, int &S, int &k) {
+    if (B < 1 || N < 2) return fail(PDSC_ERR_ARG, "B=%d N=%d (need B >= 1, N >= 2)", B, N);
+    if (N > 32767) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > 32767 (32-bit buffer descriptors over M)", N);
+    S = (int)((double)N * cfg->ratio);  // int(num_corr * self.ratio) (:174)
+    k = std::min(cfg->k, N - 1);        // (:250)
+    if (S < 1) return fail(PDSC_ERR_ARG, "int(N*ratio) = 0 seeds for N=%d", N);
+    if (k > 63) return fail(PDSC_ERR_UNSUPPORTED, "k=%d > 63", k);
+    return PDSC_OK;
+}
+}  // namespace pdsc
+
+namespace {
+
+// pdsc_forward_timing: PDSC_FORWARD_STAGES + 1 events per forward call
+thread_local hipEvent_t *g_fev = nullptr;
+thread_local int g_fcap = 0;
+thread_local int32_t *g_fcount = nullptr;
+
 struct Dims {
     int B, N, Npad, S, k, T;
     bool f32;          // PDSC_PRECISION_F32
@@ -72,242 +76,16 @@ struct Dims {
     TailPlan tail;     // the tail's plan for (B, N, S)
 };
 
-// dense_m_caller: the standalone encoder's plan, on the caller's dense M (plan_encoder)
-int make_dims(const pdsc_config *cfg, int B, int N, Dims &d, bool dense_m_caller = false) {
-    if (B < 1 || N < 2) return fail(PDSC_ERR_ARG, "B=%d N=%d (need B >= 1, N >= 2)", B, N);
-    if (N > 32767) return fail(PDSC_ERR_UNSUPPORTED, "N=%d > 32767 (32-bit buffer descriptors over M)", N);
+int make_dims(const pdsc_config *cfg, int B, int N, Dims &d) {
+    RET_IF(check_shape(cfg, B, N, d.S, d.k));
     d.B = B;
     d.N = N;
     d.Npad = round_up(N, QB);
-    d.S = (int)((double)N * cfg->ratio);  // int(num_corr * self.ratio) (:174)
-    d.k = std::min(cfg->k, N - 1);        // (:250)
     d.T = cfg->num_iterations;
     d.f32 = cfg->precision == PDSC_PRECISION_F32;
-    d.plan = plan_encoder(B, N, d.f32, dense_m_caller);
+    d.plan = plan_encoder(B, N, d.f32, false);
     d.tail = plan_tail(B, N, d.S);
-    if (d.S < 1) return fail(PDSC_ERR_ARG, "int(N*ratio) = 0 seeds for N=%d", N);
-    if (d.k > 63) return fail(PDSC_ERR_UNSUPPORTED, "k=%d > 63", d.k);
     return PDSC_OK;
-}
-
-struct EncBufs {
-    float *feat, *opart, *ml, *vexp, *vexp2;
-    float *feat2;            // the split path's second feat buffer (pw_mid reads one, writes the other), else null
-    _Float16 *q, *k, *v;     // attention_h3 split layouts (hi + lo per element), or fp32 rows (F32)
-    _Float16 *q2, *k2, *v2;  // the other Q/K/V set of the fused path (layers alternate), else null
-    float *opart1, *ml1;     // the combined split (EncoderPlan::precombine), else null
-};
-
-EncBufs carve_encoder(Carve &c, const Dims &d) {
-    EncBufs e;
-    const size_t rows = (size_t)d.B * d.Npad * CH;
-    e.feat = c.take<float>(rows);
-    e.q = c.take<_Float16>(2 * rows);
-    e.k = c.take<_Float16>(2 * rows);
-    e.v = c.take<_Float16>(2 * rows);
-    e.opart = c.take<float>(rows * d.plan.nsplit);
-    e.ml = c.take<float>((size_t)d.B * d.Npad * d.plan.nsplit * 2);
-    e.vexp = c.take<float>((size_t)d.B * (d.Npad / 32));
-    e.opart1 = d.plan.precombine ? c.take<float>(rows) : nullptr;
-    e.ml1 = d.plan.precombine ? c.take<float>((size_t)d.B * d.Npad * 2) : nullptr;
-    e.q2 = e.k2 = e.v2 = nullptr;
-    e.vexp2 = nullptr;
-    // pw_mid's three Q / K / V workgroups per point tile all read the layer's
-    // residual rows while one of them writes the new PointCN rows: the rows
-    // ping-pong between feat and feat2 so no workgroup overwrites what another
-    // still reads
-    e.feat2 = d.plan.fused() ? nullptr : c.take<float>(rows);
-    if (d.plan.fused()) {
-        e.q2 = c.take<_Float16>(2 * rows);
-        e.k2 = c.take<_Float16>(2 * rows);
-        e.v2 = c.take<_Float16>(2 * rows);
-        e.vexp2 = c.take<float>((size_t)d.B * (d.Npad / 32));
-    }
-    return e;
-}
-
-// M: in the plan's layout (d.plan.m_layout)
-int run_encoder(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M, const Dims &d,
-                const EncBufs &e, float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
-                Ragged rg = {}) {
-    const EncoderPlan plan = d.plan.for_ragged(rg);
-    HIPCHK(launch_pw_first(plan, packed, lay, corr_pos, e.feat, e.q, e.k, e.v, e.vexp, s, rg));
-    if (plan.fused()) {  // every layer fused (0 .. L-2 with the next layer's PointCN/QKV, Q/K/V alternating between the two sets)
-        _Float16 *q = e.q, *k = e.k, *v = e.v, *q2 = e.q2, *k2 = e.k2, *v2 = e.v2;
-        float *vx = e.vexp, *vx2 = e.vexp2;
-        for (int l = 0; l + 1 < lay.L; ++l) {
-            const bool timed = g_tcap > 0 && g_tcount && *g_tcount < g_tcap;
-            if (timed) HIPCHK(hipEventRecord(g_tstart[*g_tcount], s));
-            HIPCHK(launch_attn_pw2(plan, packed, lay, l, q, k, v, vx, M, e.feat, q2, k2, v2, vx2, s, rg));
-            if (timed) HIPCHK(hipEventRecord(g_tstop[(*g_tcount)++], s));
-            std::swap(q, q2);
-            std::swap(k, k2);
-            std::swap(v, v2);
-            std::swap(vx, vx2);
-        }
-        HIPCHK(launch_attn_pw2_last(plan, packed, lay, q, k, v, vx, M, e.feat, feat_out, normed, normed_s, conf, s, rg));
-        return PDSC_OK;
-    }
-    float *feat = e.feat, *feat_alt = e.feat2;
-    for (int l = 0; l < lay.L; ++l) {
-        const bool timed = g_tcap > 0 && g_tcount && *g_tcount < g_tcap;
-        if (timed) HIPCHK(hipEventRecord(g_tstart[*g_tcount], s));
-        HIPCHK(launch_attention(plan, e.q, e.k, e.v, e.vexp, M, e.opart, e.ml, s, rg, l));
-        if (timed) HIPCHK(hipEventRecord(g_tstop[(*g_tcount)++], s));
-        const float *op = e.opart, *mlp = e.ml;
-        int ns = plan.nsplit;
-        if (plan.precombine) {
-            HIPCHK(launch_combine_rows(e.opart, e.ml, d.B, d.Npad, plan.nsplit, e.opart1, e.ml1, s));
-            op = e.opart1;
-            mlp = e.ml1;
-            ns = 1;
-        }
-        if (l + 1 < lay.L) {
-            HIPCHK(launch_pw_mid(plan, packed, lay, l, op, mlp, ns, feat, feat_alt, e.q, e.k, e.v, e.vexp, s));
-            std::swap(feat, feat_alt);
-        } else {
-            HIPCHK(launch_pw_last(plan, packed, lay, op, mlp, ns, feat, feat_out, normed, d.f32 ? nullptr : normed_s,
-                                  conf, s));
-        }
-    }
-    return PDSC_OK;
-}
-
-// Ragged batches run the fused encoder as P parts of the batch (contiguous pair
-// ranges of equal pair counts), each on its own
-// stream -- the caller's and P - 1 per-device side streams, forked and joined
-// by events -- so one part's launches fill the others' dispatch tails: a ragged
-// batch's attention launches end in a tail of a few long workgroups per XCD
-// (DESIGN.md §7).  Pairs are independent through the encoder, so each part is
-// the same arithmetic on its own pointer range (bitwise equal results).
-// 128 pairs, N in [700, 1300], two halves: 4.54 -> 4.12 ms per forward (three
-// parts 4.23, four 4.32 vs two 4.19 on another box); uniform batches (two full
-// rounds of workgroups, no tail to fill) measured 3.77 -> 3.83 ms, so they stay
-// on one stream.  Knobs: PDSC_ENC_HALVES 0 never, 1 uniform batches too;
-// PDSC_ENC_PARTS P in [2, 4] (default 2).  Every part keeps the whole batch's
-// plan (the fused launches' one key split, pw2_first's layouts).
-static bool enc_halves(const Dims &d, bool ragged) {
-    const Knobs &k = knobs();
-    return d.plan.fused() && d.B >= 16 * k.enc_parts && (k.enc_halves == 1 || (k.enc_halves != 0 && ragged));
-}
-// Part boundaries bounds[0 .. P]: bounds[i] = the first pair whose work prefix
-// reaches i/P of the total (counts: HOST sizes, or NULL for a uniform batch).
-static void enc_bounds(const int32_t *counts, int B, int P, int *bounds) {
-    std::vector<double> pre(B + 1, 0.0);
-    for (int b = 0; b < B; ++b) pre[b + 1] = pre[b] + (counts ? (double)counts[b] * counts[b] : 1.0);
-    bounds[0] = 0;
-    bounds[P] = B;
-    for (int i = 1; i < P; ++i) {
-        const double goal = pre[B] * i / P;
-        int h = bounds[i - 1] + 1;
-        while (h < B - (P - i) && std::abs(pre[h + 1] - goal) < std::abs(pre[h] - goal)) ++h;
-        bounds[i] = h;
-    }
-}
-
-struct SideStream {
-    std::mutex mu;  // one fork / join enqueued at a time per device
-    hipStream_t s2[ENC_MAX_PARTS - 1] = {};
-    hipEvent_t fork = nullptr, join[ENC_MAX_PARTS - 1] = {};
-    bool ok = false;
-};
-// The side streams of the device that stream s runs on (the current device for
-// the legacy default stream), created there on first use.
-static SideStream *side_stream(hipStream_t s) {
-    static SideStream ss[64];
-    hipDevice_t dev = 0;
-    if (!s || hipStreamGetDevice(s, &dev) != hipSuccess)
-        if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    if (dev < 0 || dev >= 64) return nullptr;
-    SideStream &x = ss[dev];
-    static std::mutex create_mu;
-    std::lock_guard<std::mutex> lock(create_mu);
-    if (!x.ok) {  // all or none (a failure leaves the forward on one stream)
-        int cur = dev;
-        if (hipGetDevice(&cur) != hipSuccess || (cur != dev && hipSetDevice(dev) != hipSuccess)) return nullptr;
-        bool ok = x.fork || hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; ok && i < ENC_MAX_PARTS - 1; ++i) {
-            if (!x.s2[i]) ok = hipStreamCreateWithFlags(&x.s2[i], hipStreamNonBlocking) == hipSuccess;
-            if (ok && !x.join[i]) ok = hipEventCreateWithFlags(&x.join[i], hipEventDisableTiming) == hipSuccess;
-        }
-        if (cur != dev) (void)hipSetDevice(cur);
-        x.ok = ok;
-    }
-    return x.ok ? &x : nullptr;
-}
-
-// The fused plan's encoder over pairs [b0, b0 + nb): every per-pair pointer
-// moved to pair b0 (the pair-major layouts of carve_encoder / carve_forward).
-static int run_encoder_part(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M,
-                            const Dims &d, const EncBufs &e, float *normed, _Float16 *normed_s, float *conf,
-                            hipStream_t s, Ragged rg, int b0, int nb) {
-    Dims dh = d;
-    dh.B = nb;
-    dh.plan = d.plan.for_pairs(nb);  // the batch's plan, not nb pairs' own
-    const size_t rows = (size_t)b0 * d.Npad * CH;
-    EncBufs eh = e;
-    eh.feat = e.feat + rows;
-    eh.q = e.q + 2 * rows;
-    eh.k = e.k + 2 * rows;
-    eh.v = e.v + 2 * rows;
-    eh.q2 = e.q2 + 2 * rows;
-    eh.k2 = e.k2 + 2 * rows;
-    eh.v2 = e.v2 + 2 * rows;
-    eh.vexp = e.vexp + (size_t)b0 * (d.Npad / 32);
-    eh.vexp2 = e.vexp2 + (size_t)b0 * (d.Npad / 32);
-    const size_t mstr = d.plan.m_layout == M_PACKED ? mpack_floats(d.N) : (size_t)d.N * d.N;
-    Ragged rh = rg;
-    if (rg.nv) rh.nv = rg.nv + b0;
-    if (rg.sv) rh.sv = rg.sv + b0;
-    if (rg.po) rh.po = rg.po + b0;
-    return run_encoder(lay, packed, corr_pos + (size_t)b0 * d.N * lay.in_dim, M + (size_t)b0 * mstr, dh, eh, nullptr,
-                       normed + (size_t)b0 * d.N * CH, normed_s + (size_t)b0 * d.N * 2 * CH, conf + (size_t)b0 * d.N, s,
-                       rh);
-}
-
-// run_encoder for the forward: the fused plan as P concurrent parts given side
-// streams ss and the part boundaries (enc_halves / enc_bounds; rg.po, when set,
-// must then order each part's pairs on its own: launch_ragged_order per part),
-// else run_encoder itself.
-static int run_encoder_fwd(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M,
-                           const Dims &d, const EncBufs &e, float *normed, _Float16 *normed_s, float *conf,
-                           hipStream_t s, Ragged rg, SideStream *ss, const int *bounds, int P) {
-    if (!ss) return run_encoder(lay, packed, corr_pos, M, d, e, nullptr, normed, normed_s, conf, s, rg);
-    std::lock_guard<std::mutex> lock(ss->mu);
-    // The side streams are shared by every caller stream of the device.  A side
-    // stream forked into another thread's graph capture stays in that capture
-    // until it ends: enqueueing there from a stream outside that capture would
-    // record into (or invalidate) the other graph, so such a call runs on one
-    // stream (bitwise the same results).
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone, c2 = hipStreamCaptureStatusNone;
-        unsigned long long id = 0, id2 = 0;
-        HIPCHK(hipStreamGetCaptureInfo(s, &cs, &id));
-        for (int i = 1; i < P; ++i) {
-            HIPCHK(hipStreamGetCaptureInfo(ss->s2[i - 1], &c2, &id2));
-            if (c2 != hipStreamCaptureStatusNone && (cs != hipStreamCaptureStatusActive || id2 != id))
-                return run_encoder(lay, packed, corr_pos, M, d, e, nullptr, normed, normed_s, conf, s, rg);
-        }
-    }
-    HIPCHK(hipEventRecord(ss->fork, s));
-    int forked = 1, r = PDSC_OK;
-    for (; forked < P; ++forked)
-        if (hipStreamWaitEvent(ss->s2[forked - 1], ss->fork, 0) != hipSuccess) {
-            r = fail(PDSC_ERR_HIP, "hipStreamWaitEvent (fork)");
-            break;
-        }
-    for (int i = 0; r == PDSC_OK && i < P; ++i)
-        r = run_encoder_part(lay, packed, corr_pos, M, d, e, normed, normed_s, conf, i ? ss->s2[i - 1] : s, rg,
-                             bounds[i], bounds[i + 1] - bounds[i]);
-    // join every side stream that was forked, on success AND on error: the
-    // caller's stream must not run ahead of work a side stream may still do in
-    // the workspace, and a capture must not end with an unjoined fork
-    for (int i = 1; i < forked; ++i) {
-        const hipError_t a = hipEventRecord(ss->join[i - 1], ss->s2[i - 1]);
-        const hipError_t b = a == hipSuccess ? hipStreamWaitEvent(s, ss->join[i - 1], 0) : a;
-        if (b != hipSuccess && r == PDSC_OK) r = fail(PDSC_ERR_HIP, "join: %s", hipGetErrorString(b));
-    }
-    return r;
 }
 
 struct FwdBufs {
@@ -325,7 +103,7 @@ FwdBufs carve_forward(Carve &c, const Dims &d) {
     f.range = c.take<int>((size_t)d.B);  // first: at the workspace's base
     // symmetric-packed tiles (PDSC_DENSE_M=1: the dense [N][N] form, for A/B measurement)
     f.M = c.take<float>((size_t)d.B * std::max(mpack_floats(d.N), (size_t)d.N * d.N));  // packed or dense
-    f.enc = carve_encoder(c, d);
+    f.enc = carve_encoder(c, d.plan);
     f.normed = c.take<float>((size_t)d.B * d.N * CH);
     f.normed_s = c.take<_Float16>((size_t)d.B * d.N * 2 * CH);
     f.conf = c.take<float>((size_t)d.B * d.N);
@@ -351,212 +129,11 @@ extern "C" {
 const char *pdsc_version(void) { return "pdsc 0.1.0 gfx950"; }
 const char *pdsc_last_error(void) { return g_err.c_str(); }
 
-// ------------------------------------------------------------------ weights
-int32_t pdsc_param_count(const pdsc_config *cfg) { return cfg ? 10 + 26 * cfg->num_layers : -1; }
-
-const char *pdsc_param_name(const pdsc_config *cfg, int32_t i) {
-    if (!cfg || i < 0 || i >= pdsc_param_count(cfg)) return nullptr;
-    static const char *bn[] = {"weight", "bias", "running_mean", "running_var"};
-    static const char *per[] = {"fc_message.0.weight", "fc_message.0.bias", "fc_message.1.weight",
-                                "fc_message.1.bias", "fc_message.1.running_mean", "fc_message.1.running_var",
-                                "fc_message.3.weight", "fc_message.3.bias", "fc_message.4.weight",
-                                "fc_message.4.bias", "fc_message.4.running_mean", "fc_message.4.running_var",
-                                "fc_message.6.weight", "fc_message.6.bias", "projection_q.weight",
-                                "projection_q.bias", "projection_k.weight", "projection_k.bias",
-                                "projection_v.weight", "projection_v.bias"};
-    static const char *tail[] = {"encoder.layer0.weight", "encoder.layer0.bias", "classification.0.weight",
-                                 "classification.0.bias", "classification.2.weight", "classification.2.bias",
-                                 "classification.4.weight", "classification.4.bias"};
-    const int L = cfg->num_layers;
-    if (i == 0) return "sigma";
-    if (i == 1) return "sigma_spat";
-    i -= 2;
-    if (i < 26 * L) {
-        const int l = i / 26, o = i % 26;
-        char buf[128];
-        if (o < 2)
-            snprintf(buf, sizeof(buf), "encoder.blocks.PointCN_layer_%d.0.%s", l, o == 0 ? "weight" : "bias");
-        else if (o < 6)
-            snprintf(buf, sizeof(buf), "encoder.blocks.PointCN_layer_%d.1.%s", l, bn[o - 2]);
-        else
-            snprintf(buf, sizeof(buf), "encoder.blocks.NonLocal_layer_%d.%s", l, per[o - 6]);
-        g_name = buf;
-        return g_name.c_str();
-    }
-    return tail[i - 26 * L];
-}
-
-size_t pdsc_packed_weights_floats(const pdsc_config *cfg) {
-    if (check_cfg(cfg) != PDSC_OK) return 0;
-    return make_layout(cfg->num_layers, cfg->in_dim).total;
-}
-
-int32_t pdsc_pack_weights(const pdsc_config *cfg, const float *const *P, float *packed,
-                          pdsc_stream_t stream) {
-    RET_IF(check_cfg(cfg));
-    if (!P || !packed) return fail(PDSC_ERR_ARG, "null params/packed");
-    const int n = pdsc_param_count(cfg);
-    for (int i = 0; i < n; ++i)
-        if (!P[i]) return fail(PDSC_ERR_ARG, "param %d (%s) is NULL", i, pdsc_param_name(cfg, i));
-    hipStream_t s = S_(stream);
-    const PackLayout lay = make_layout(cfg->num_layers, cfg->in_dim);
-    HIPCHK(hipMemsetAsync(packed, 0, lay.total * sizeof(float), s));
-    HIPCHK(launch_copy(P[0], packed + lay.sigma, 1, s));
-    HIPCHK(launch_copy(P[1], packed + lay.sigma_d, 1, s));
-    const bool f32 = cfg->precision == PDSC_PRECISION_F32;
-    auto dense = [&](const DenseOff &o, int wi, int in, int out, bool has_bn) -> hipError_t {
-        return launch_pack_dense(P[wi], P[wi + 1], has_bn ? P[wi + 2] : nullptr,
-                                 has_bn ? P[wi + 3] : nullptr, has_bn ? P[wi + 4] : nullptr,
-                                 has_bn ? P[wi + 5] : nullptr, in, out, f32, packed + o.w, packed + o.bias,
-                                 packed + o.alpha, packed + o.beta, packed + o.scale, s);
-    };
-    float *fold_tmp = nullptr;
-    HIPCHK(hipMallocAsync(reinterpret_cast<void **>(&fold_tmp), ((size_t)CH2 * CH + CH2) * sizeof(float), s));
-    for (int l = 0; l < cfg->num_layers; ++l) {
-        const int b = 2 + 26 * l;
-        const LayerOff &lo = lay.layer[l];
-        HIPCHK(dense(lo.pcn, b + 0, CH, CH, true));
-        HIPCHK(dense(lo.fc0, b + 6, CH, CH2, true));
-        HIPCHK(dense(lo.fc3, b + 12, CH2, CH2, true));
-        HIPCHK(dense(lo.fc6, b + 18, CH2, CH, false));
-        HIPCHK(dense(lo.q, b + 20, CH, CH, false));
-        HIPCHK(dense(lo.k, b + 22, CH, CH, false));
-        HIPCHK(dense(lo.v, b + 24, CH, CH, false));
-        // the V fold: W0 Wv and W0 bv + b0 (fp64, rounded once) packed as a dense block
-        // of their own, with fc0's BatchNorm (launch_pack_dense takes the scale from W0 Wv)
-        // (wm, bm: a stream-ordered temporary of the call)
-        float *wm = fold_tmp, *bm = wm + (size_t)CH2 * CH;
-        HIPCHK(launch_fold_vm(P[b + 6], P[b + 7], P[b + 24], P[b + 25], wm, bm, s));
-        HIPCHK(launch_pack_dense(wm, bm, P[b + 8], P[b + 9], P[b + 10], P[b + 11], CH, CH2, f32, packed + lo.vm.w,
-                                 packed + lo.vm.bias, packed + lo.vm.alpha, packed + lo.vm.beta, packed + lo.vm.scale, s));
-    }
-    HIPCHK(hipFreeAsync(fold_tmp, s));
-    const int t = 2 + 26 * cfg->num_layers;
-    HIPCHK(launch_copy(P[t], packed + lay.l0_w, CH * cfg->in_dim, s));
-    HIPCHK(launch_copy(P[t + 1], packed + lay.l0_b, CH, s));
-    HIPCHK(dense(lay.c0, t + 2, CH, CLS, false));
-    HIPCHK(dense(lay.c2, t + 4, CLS, CLS, false));
-    HIPCHK(launch_copy(P[t + 6], packed + lay.c4_w, CLS, s));
-    HIPCHK(launch_copy(P[t + 7], packed + lay.c4_b, 1, s));
-    return PDSC_OK;
-}
-
-// ---------------------------------------------------------------- a2-a4
-// (the standalone encoder takes the caller's dense M: make_dims' dense_m_caller)
-size_t pdsc_encoder_workspace_bytes(const pdsc_config *cfg, int32_t B, int32_t N) {
-    Dims d;
-    if (check_cfg(cfg) != PDSC_OK || make_dims(cfg, B, N, d, true) != PDSC_OK) return 0;
-    Carve c(nullptr);
-    carve_encoder(c, d);
-    return c.off;
-}
-
-int32_t pdsc_encoder_f32(const pdsc_config *cfg, const float *packed, const float *corr_pos,
-                         const float *M, int32_t B, int32_t N, float *feat, float *normed, float *conf,
-                         void *ws, size_t ws_bytes, pdsc_stream_t stream) {
-    RET_IF(check_cfg(cfg));
-    Dims d;
-    RET_IF(make_dims(cfg, B, N, d, true));
-    if (!packed || !corr_pos || !M || !normed || !conf || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    RET_IF(need_ws(ws_bytes, pdsc_encoder_workspace_bytes(cfg, B, N)));
-    Carve c(ws);
-    const EncBufs e = carve_encoder(c, d);
-    const PackLayout lay = make_layout(cfg->num_layers, cfg->in_dim);
-    return run_encoder(lay, packed, corr_pos, M, d, e, feat, normed, nullptr, conf, S_(stream));
-}
-
-size_t pdsc_attention_workspace_bytes(int32_t B, int32_t N, int32_t C, int32_t precision) {
-    if (C != CH || B < 1 || N < 1 || (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)) return 0;
-    const int Npad = round_up(N, QB), ns = plan_encoder(B, N, precision == PDSC_PRECISION_F32, true, false).nsplit;
-    Carve c(nullptr);
-    for (int i = 0; i < 3; ++i) c.take<_Float16>((size_t)2 * B * Npad * CH);
-    c.take<float>((size_t)B * Npad * CH * ns);
-    c.take<float>((size_t)B * Npad * ns * 2);
-    c.take<float>((size_t)B * (Npad / 32));
-    return c.off;
-}
-
-int32_t pdsc_attention_f32(const float *q, const float *k, const float *v, const float *M, int32_t B,
-                           int32_t N, int32_t C, int32_t precision, float *msg, void *ws, size_t ws_bytes,
-                           pdsc_stream_t stream) {
-    if (C != CH) return fail(PDSC_ERR_UNSUPPORTED, "C=%d (only %d)", C, CH);
-    if (!q || !k || !v || !M || !msg || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    if (B < 1 || N < 1 || N > 32767) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
-        return fail(PDSC_ERR_ARG, "precision=%d", precision);
-    RET_IF(need_ws(ws_bytes, pdsc_attention_workspace_bytes(B, N, C, precision)));
-    hipStream_t s = S_(stream);
-    const bool f32 = precision == PDSC_PRECISION_F32;
-    const EncoderPlan plan = plan_encoder(B, N, f32, true, false);  // the split launch on the caller's dense M
-    const int Npad = plan.Npad, ns = plan.nsplit;
-    Carve c(ws);
-    _Float16 *qs = c.take<_Float16>((size_t)2 * B * Npad * CH);
-    _Float16 *ks = c.take<_Float16>((size_t)2 * B * Npad * CH);
-    _Float16 *vs = c.take<_Float16>((size_t)2 * B * Npad * CH);
-    float *op = c.take<float>((size_t)B * Npad * CH * ns);
-    float *ml = c.take<float>((size_t)B * Npad * ns * 2);
-    float *vexp = c.take<float>((size_t)B * (Npad / 32));
-    if (f32) {  // the caller's rows, zero-padded to Npad rows (the same bytes as the split layouts)
-        HIPCHK(launch_pad_rows(q, B, N, Npad, reinterpret_cast<float *>(qs), s));
-        HIPCHK(launch_pad_rows(k, B, N, Npad, reinterpret_cast<float *>(ks), s));
-        HIPCHK(launch_pad_rows(v, B, N, Npad, reinterpret_cast<float *>(vs), s));
-    } else {  // the caller's fp32 [B][N][C] rows -> the kernel's padded fp16 hi/lo layouts
-        HIPCHK(launch_split_qkv(q, k, v, B, N, N, Npad, qs, ks, vs, vexp, s));
-    }
-    HIPCHK(launch_attention(plan, qs, ks, vs, vexp, M, op, ml, s));
-    HIPCHK(launch_attn_combine(op, ml, f32, B, N, Npad, ns, msg, s));
-    return PDSC_OK;
-}
-
-int32_t pdsc_attention_timing(void *const *start_events, void *const *stop_events, int32_t capacity,
-                              int32_t *count) {
-    if (capacity > 0 && (!start_events || !stop_events || !count))
-        return fail(PDSC_ERR_ARG, "null events/count with capacity %d", capacity);
-    g_tstart = reinterpret_cast<hipEvent_t *>(const_cast<void **>(start_events));
-    g_tstop = reinterpret_cast<hipEvent_t *>(const_cast<void **>(stop_events));
-    g_tcap = capacity;
-    g_tcount = count;
-    return PDSC_OK;
-}
-
-int32_t pdsc_diag_qkv_delay(int32_t loops) {
-    if (loops < 0) return fail(PDSC_ERR_ARG, "loops=%d", loops);
-    g_diag_qkv_delay = loops;
-    return PDSC_OK;
-}
-
 int32_t pdsc_forward_timing(void *const *events, int32_t capacity, int32_t *count) {
     if (capacity > 0 && (!events || !count)) return fail(PDSC_ERR_ARG, "null events/count with capacity %d", capacity);
     g_fev = reinterpret_cast<hipEvent_t *>(const_cast<void **>(events));
     g_fcap = capacity;
     g_fcount = count;
-    return PDSC_OK;
-}
-
-int32_t pdsc_attention_layout(int32_t B, int32_t N, int32_t precision, int32_t *Npad, int32_t *nsplit) {
-    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
-        return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
-    if (B < 1 || N < 1 || !Npad || !nsplit) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    const EncoderPlan plan = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false);
-    *Npad = plan.Npad;
-    *nsplit = plan.nsplit;
-    return PDSC_OK;
-}
-
-int32_t pdsc_encoder_plan(int32_t B, int32_t N, int32_t precision, int32_t *fused) {
-    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
-        return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
-    if (B < 1 || N < 1 || !fused) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    const EncoderPlan plan = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false);
-    *fused = plan.fused() ? 1 : (plan.w64() ? 2 : 0);
-    return PDSC_OK;
-}
-
-int32_t pdsc_encoder_plan_vfold(int32_t B, int32_t N, int32_t precision, int32_t *vfold) {
-    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
-        return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
-    if (B < 1 || N < 1 || !vfold) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
-    *vfold = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false).vfold ? 1 : 0;
     return PDSC_OK;
 }
 
@@ -572,17 +149,6 @@ int32_t pdsc_launch_plan(const pdsc_config *cfg, int32_t B, int32_t N, int32_t *
                                                   p.pw_prefetch, t.seed_rows, t.nms_rpt, (int32_t)t.rank, t.wpb,
                                                   t.knn_bitonic, t.kabsch_fused, t.tail_fused};
     std::copy(row, row + PDSC_LAUNCH_PLAN_FIELDS, out);
-    return PDSC_OK;
-}
-
-int32_t pdsc_packed_block(const pdsc_config *cfg, int32_t layer, int32_t block, size_t offsets[5]) {
-    RET_IF(check_cfg(cfg));
-    if (layer < 0 || layer >= cfg->num_layers || block < 0 || block > 7 || !offsets)
-        return fail(PDSC_ERR_ARG, "layer=%d block=%d", layer, block);
-    const LayerOff lo = make_layout(cfg->num_layers, cfg->in_dim).layer[layer];
-    const DenseOff d[8] = {lo.pcn, lo.fc0, lo.fc3, lo.fc6, lo.q, lo.k, lo.v, lo.vm};
-    const DenseOff &o = d[block];
-    offsets[0] = o.w, offsets[1] = o.bias, offsets[2] = o.alpha, offsets[3] = o.beta, offsets[4] = o.scale;
     return PDSC_OK;
 }
 
@@ -632,7 +198,7 @@ static int32_t forward_testing_impl(const pdsc_config *cfg, const float *packed,
     Carve c(ws);
     const FwdBufs f = carve_forward(c, d);
     Ragged rg;
-    SideStream *halves = enc_halves(d, counts != nullptr) ? side_stream(s) : nullptr;
+    SideStream *halves = enc_halves(d.plan, counts != nullptr) ? side_stream(s) : nullptr;
     const int parts = halves ? knobs().enc_parts : 1;
     int bounds[ENC_MAX_PARTS + 1] = {0, B};
     if (halves) enc_bounds(knobs().enc_bal ? counts : nullptr, B, parts, bounds);
@@ -664,7 +230,7 @@ static int32_t forward_testing_impl(const pdsc_config *cfg, const float *packed,
         HIPCHK(launch_compat(src, tgt, d.B, d.N, sigma_d, f.M, s, rg));
     STAGE(1);
     // a2-a4 (:155-156, :171)
-    RET_IF(run_encoder_fwd(lay, packed, corr_pos, f.M, d, f.enc, f.normed, f.normed_s, f.conf, s, rg, halves,
+    RET_IF(run_encoder_fwd(lay, packed, corr_pos, f.M, d.plan, f.enc, f.normed, f.normed_s, f.conf, s, rg, halves,
                            bounds, parts));
     STAGE(2);
     // a5 (:174)
@@ -762,7 +328,7 @@ int32_t pdsc_forward_training(const pdsc_config *cfg, const float *packed, const
         HIPCHK(launch_compat_packed(src, tgt, d.B, d.N, sigma_d, f.M, s));
     else
         HIPCHK(launch_compat(src, tgt, d.B, d.N, sigma_d, f.M, s));
-    RET_IF(run_encoder(lay, packed, corr_pos, f.M, d, f.enc, nullptr, f.normed, f.normed_s, f.conf, s));
+    RET_IF(run_encoder_fwd(lay, packed, corr_pos, f.M, d.plan, f.enc, f.normed, f.normed_s, f.conf, s));
     // the loss's feature-similarity M (:158-163)
     if (M_out)
         HIPCHK(launch_feat_sim(d.f32 ? static_cast<const void *>(f.normed) : static_cast<const void *>(f.normed_s),

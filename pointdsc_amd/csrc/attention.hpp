@@ -1,7 +1,7 @@
 // attention.hpp -- the SCNonlocal attention core (models/PointDSC.py:36-42),
 // flash-style on fp32 MFMA, as a template so variants can be A/B-timed in one
 // process (tools/attn_bench.hip).  The production instantiation is chosen in
-// encoder.hip.
+// attention.hip (launch_attention).
 //
 //   msg_i = sum_j softmax_j( M_ij * (q_i . k_j) / sqrt(C) ) v_j,   C = 128, heads = 1
 //

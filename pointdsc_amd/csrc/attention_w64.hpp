@@ -188,7 +188,7 @@ constexpr size_t W64_ST_LDS = 0;
     } while (0)
 #endif
 
-// split2 (attention_h3.hpp) as three single-instruction statements, so a
+// split2 (h3.hpp) as three single-instruction statements, so a
 // softmax slice carries one of them: hi = {f16(x0), f16(x1)}, then lo's halves
 // by v_fma_mixlo / v_fma_mixhi (x - hi exact, one rounding).  No s_nop: the P
 // fragments are read by the MFMAs of the NEXT region, many states later.

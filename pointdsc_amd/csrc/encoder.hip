@@ -3,7 +3,7 @@
 // Replaces models/PointDSC.py:9-77 (NonLocalBlock / NonLocalNet), :155-156 and
 // :171.  Layout in HBM (per pair b, N padded to Npad = round_up(N,128) rows):
 //   feat          : [B][Npad][128] fp32, point-major (row = correspondence)
-//   Qs, Ks, Vs    : the fp16 hi/lo split layouts of attention_h3.hpp (4 B/element)
+//   Qs, Ks, Vs    : the fp16 hi/lo split layouts of h3.hpp (4 B/element)
 //   M             : [B][N][N] fp32 (a1 output; symmetric)
 //   opart, ml     : [B][nsplit][Npad][128], [B][nsplit][Npad][2] attention partials
 //
@@ -11,7 +11,7 @@
 // attention_l (+ pw_mid_l = combine + fc_message_l + residual + PointCN_{l+1}
 // + QKV_{l+1}), and pw_last (combine + fc_message + residual + normalize +
 // classifier).  The pointwise products run on v_mfma_f32_32x32x16_f16 with the
-// 3-product split of attention_h3.hpp (activations split as read from LDS,
+// 3-product split of h3.hpp (activations split as read from LDS,
 // weights pre-split and power-of-two scaled at pack time); their Q/K/V
 // epilogues write the fp16 hi/lo splits that the attention consumes.
 //
@@ -22,142 +22,24 @@
 // symmetric => coalesced 128-B rows); incompatible pairs keep logit 0 (not
 // -inf) exactly as :41; online softmax with a lazily re-based running max;
 // split-K over keys when B*N is too small to fill 256 CUs.
+//
+// This file: the plan (plan_encoder), the register-chained pointwise chain and
+// the fused attention + chain kernels, the launch_pw_* dispatchers, the row's
+// run loop (run_encoder, its parts on side streams) and its entry points.
+// pack.hip packs the weights, attention.hip launches the split attention,
+// pw_lds.hpp holds the LDS-tiled chain.
+#include <algorithm>
 #include <cstdlib>
-#include <type_traits>
+#include <mutex>
+#include <vector>
 
-#include "attention.hpp"
-#include "attention_h3.hpp"
-#include "launch_plan.hpp"
-#include "attention_w64.hpp"
+#include "abi.hpp"
+#include "encoder.hpp"
+#include "pw_lds.hpp"
 
 namespace pdsc {
 
-// ============================================================ weight packing
-// Per-layer power-of-two scale: max|W| 2^s <= 2^14 keeps hi and (for all but
-// the weights 2^-17 below the layer's largest) lo in fp16's normal range.
-__global__ __launch_bounds__(256) void wscale_kernel(const float *__restrict__ w, int n, int f32,
-                                                     float *__restrict__ sc) {
-    __shared__ float part[4];
-    if (f32) {  // exact-fp32 weights are stored unscaled
-        if (threadIdx.x == 0) sc[0] = sc[1] = 1.0f;
-        return;
-    }
-    float m = 0.0f;
-    for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(w[i]));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
-        int ex = 0;
-        if (m > 0.0f && m < INFINITY) frexpf(m, &ex);  // m < 2^ex
-        const int sh = max(-100, min(100, 14 - ex));
-        sc[0] = ldexpf(1.0f, -sh);
-        sc[1] = ldexpf(1.0f, sh);
-    }
-}
-
-// W [out][in] (torch Conv1d weight) -> W_PLANES fp16 planes hi, mid (, lo) of
-// W * 2^s ~= hi + mid (22 significant bits; with lo: 33, every fp32 weight
-// exactly) in MFMA-fragment blocks (w3_index, pdsc_internal.hpp): block (t, ks)
-// = outputs 32t..32t+31 x the 16 inputs of k-step ks, planes of 1 KiB
-// each, lane (h, n)'s 16 B = positions 8h .. 8h+7 of output 32t + n in qk_pos
-// order (bits 2 and 3 of the input index swapped: inputs {4h..4h+3,
-// 8+4h..8+4h+3} of the k-step, exactly the channels a transposed product's
-// accumulator half h holds).  Blocks are stored t-major, so any run of
-// consecutive blocks is one contiguous copy (f32: W itself, fp32 [out][in]).
-// BN folded as torch-CPU eval folds it.
-__global__ void pack_dense_kernel(const float *__restrict__ w, const float *__restrict__ b,
-                                  const float *__restrict__ bn_w, const float *__restrict__ bn_b,
-                                  const float *__restrict__ bn_rm, const float *__restrict__ bn_rv,
-                                  int in, int out, int f32, float *__restrict__ dw, float *__restrict__ db,
-                                  float *__restrict__ da, float *__restrict__ dbeta,
-                                  const float *__restrict__ sc) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int total = in * out;
-    if (i < total && f32) {
-        dw[i] = w[i];
-    } else if (i < total) {
-        _Float16 *wd = reinterpret_cast<_Float16 *>(dw);
-        const int o = i / in, c = i % in;
-        float x = w[i] * sc[1];  // exact (power of two)
-        asm("" : "+v"(x));       // one hi for both uses (see split_h)
-        const _Float16 hi = (_Float16)x;
-        const float r1 = x - (float)hi;  // exact
-        const _Float16 mid = (_Float16)r1;
-        const size_t d = w3_index(o, c, in);
-        wd[d] = hi;
-        wd[d + 512] = mid;
-        if (W_PLANES == 3) wd[d + 1024] = (_Float16)(r1 - (float)mid);
-    }
-    if (i < out) {
-        db[i] = b[i];
-        if (bn_w) {
-            // torch-CPU eval BatchNorm: invstd = 1/sqrt(var+eps); alpha = invstd*w; beta = b - mean*alpha
-            const float invstd = 1.0f / sqrtf(bn_rv[i] + 1e-5f);
-            const float alpha = invstd * bn_w[i];
-            da[i] = alpha;
-            dbeta[i] = bn_b[i] - bn_rm[i] * alpha;
-        } else {
-            da[i] = 1.0f;
-            dbeta[i] = 0.0f;
-        }
-    }
-}
-
-__global__ void copy_kernel(const float *__restrict__ s, float *__restrict__ d, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) d[i] = s[i];
-}
-
-hipError_t launch_pack_dense(const float *w, const float *b, const float *bn_w, const float *bn_b,
-                             const float *bn_rm, const float *bn_rv, int in, int out, bool f32, float *dst_w,
-                             float *dst_b, float *dst_a, float *dst_beta, float *dst_scale, hipStream_t s) {
-    const int n = in * out;
-    hipLaunchKernelGGL(wscale_kernel, dim3(1), dim3(256), 0, s, w, n, (int)f32, dst_scale);
-    hipLaunchKernelGGL(pack_dense_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, b, bn_w, bn_b,
-                       bn_rm, bn_rv, in, out, (int)f32, dst_w, dst_b, dst_a, dst_beta, dst_scale);
-    return hipGetLastError();
-}
-
-// The V fold: wm = W0 Wv [CH2][CH] and bm = W0 bv + b0 [CH2],
-// summed in fp64 (every product of two fp32 values is exact there) and rounded
-// once to fp32.  w0 [CH2][CH]: fc_message[0]; wv [CH][CH], bv: projection_v.
-__global__ void fold_vm_kernel(const float *__restrict__ w0, const float *__restrict__ b0,
-                               const float *__restrict__ wv, const float *__restrict__ bv,
-                               float *__restrict__ wm, float *__restrict__ bm) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < CH2 * CH) {
-        const int o = i / CH, c = i % CH;
-        double acc = 0.0;
-        for (int j = 0; j < CH; ++j) acc += (double)w0[o * CH + j] * (double)wv[j * CH + c];
-        wm[i] = (float)acc;
-    }
-    if (i < CH2) {
-        double acc = (double)b0[i];
-        for (int j = 0; j < CH; ++j) acc += (double)w0[i * CH + j] * (double)bv[j];
-        bm[i] = (float)acc;
-    }
-}
-
-hipError_t launch_fold_vm(const float *w0, const float *b0, const float *wv, const float *bv, float *wm, float *bm,
-                          hipStream_t s) {
-    hipLaunchKernelGGL(fold_vm_kernel, dim3(CH2 * CH / 256), dim3(256), 0, s, w0, b0, wv, bv, wm, bm);
-    return hipGetLastError();
-}
-
-hipError_t launch_copy(const float *src, float *dst, int n, hipStream_t s) {
-    hipLaunchKernelGGL(copy_kernel, dim3((n + 255) / 256), dim3(256), 0, s, src, dst, n);
-    return hipGetLastError();
-}
-
-// ================================================================= attention
-// Production instantiation of attention_h3.hpp: 4 waves x 32 queries per
-// workgroup, XCD-aware block map.  (tools/attn_bench.hip A/B-times it against
-// the exact-fp32-MFMA kernel of attention.hpp.)
-constexpr int ATT_NW = 4;
-// PDSC_PRECISION_F32: attention.hpp's exact-fp32 MFMA kernel, 32-key stages, libm expf
-constexpr int ATT_F32_KTS = 32;
+static thread_local int g_diag_qkv_delay = 0;  // pdsc_diag_qkv_delay (tests only)
 
 // pw2 for launches of at least 320 128-point workgroups, 1.25 per CU.  Measured
 // encoder ms, pw2 vs pw_mid chains: 8 x N=5000 (320 WGs; 3 key splits) 4.48
@@ -302,206 +184,9 @@ EncoderPlan plan_encoder(int B, int N, bool f32, bool dense_m_caller, bool allow
     return p;
 }
 
-// the h3 kernels' grid argument for layer `layer` (stream-K: the uniform batch's form)
-static AttnGridH3 plan_grid_h3(const EncoderPlan &plan, const Ragged &rg, int layer) {
-    const bool sk = plan.kind == ATT_W64_SK;
-    return AttnGridH3{plan.B, plan.N, plan.Npad, plan.nqb, plan.fused() ? 1 : plan.nsplit, plan.sps,
-                      sk ? nullptr : rg.nv, sk ? nullptr : rg.po, plan.rev(rg, layer)};
-}
-
-// A run-time bool / int of the plan as a kernel template argument: f(std::bool_constant) / f(std::integral_constant).
-template <typename F> static void with_bool(bool b, F &&f) { b ? f(std::true_type{}) : f(std::false_type{}); }
-template <int V, int... Vs, typename F> static void with_int(int v, F &&f) {
-    if (v == V) f(std::integral_constant<int, V>{});
-    else if constexpr (sizeof...(Vs) > 0) with_int<Vs...>(v, f);
-}
-
-// One layer's attention as the plan says.
-hipError_t launch_attention(const EncoderPlan &plan, const void *q, const void *k, const void *v, const float *vexp,
-                            const float *M, float *opart, float *ml, hipStream_t s, Ragged rg, int layer) {
-    const dim3 grid(plan.workgroups());
-    const _Float16 *qs = static_cast<const _Float16 *>(q), *ks = static_cast<const _Float16 *>(k),
-                   *vs = static_cast<const _Float16 *>(v);
-    const AttnGridH3 g = plan_grid_h3(plan, rg, layer);
-    const bool packed = plan.m_layout == M_PACKED;
-    switch (plan.kind) {
-    case ATT_W64_SK:
-        hipLaunchKernelGGL((attention_w64_sk_kernel<true>), grid, dim3(W64_NW * 64), W64_LDS, s, qs, ks, vs, vexp, M, g,
-                           plan.sk_wgs, opart, ml);
-        break;
-    case ATT_W64:
-        hipLaunchKernelGGL((attention_w64_kernel<true>), grid, dim3(W64_NW * 64), W64_LDS, s, qs, ks, vs, vexp, M, g,
-                           opart, ml);
-        break;
-    case ATT_F32: {  // fp32 [B][Npad][CH] rows, dense M
-        const AttnGrid gf{plan.B, plan.N, plan.Npad, plan.nqb, plan.nsplit, plan.sps, rg.nv};
-        hipLaunchKernelGGL((attention_kernel_t<ATT_NW, ATT_F32_KTS, false, true>), grid, dim3(ATT_NW * 64),
-                           (attention_lds_bytes<ATT_NW, ATT_F32_KTS>()), s, static_cast<const float *>(q),
-                           static_cast<const float *>(k), static_cast<const float *>(v), M, gf, opart, ml);
-        break;
-    }
-    case ATT_H3_WS:
-        if (plan.vfold) return hipErrorInvalidValue;
-        with_int<2, 4>(plan.ws, [&](auto ws) {
-            with_bool(packed, [&](auto pk) {
-                constexpr int WS = decltype(ws)::value;
-                hipLaunchKernelGGL((attention_h3_ws_kernel<WS, decltype(pk)::value>), grid, dim3(WS * 64),
-                                   attention_h3_ws_lds_bytes<WS>(), s, qs, ks, vs, vexp, M, g, opart, ml);
-            });
-        });
-        break;
-    case ATT_H3:
-        if (plan.vfold) {  // the folded V' (the register-chained chains' plans: 4 waves)
-            if (plan.nw != ATT_NW) return hipErrorInvalidValue;
-            with_bool(plan.early, [&](auto early) {
-                with_bool(packed, [&](auto pk) {
-                    hipLaunchKernelGGL((attention_h3_kernel<ATT_NW, true, decltype(pk)::value, decltype(early)::value, CH2>),
-                                       grid, dim3(ATT_NW * 64), attention_h3_lds_bytes<ATT_NW>(), s, qs, ks, vs, vexp, M,
-                                       g, opart, ml);
-                });
-            });
-            break;
-        }
-        with_int<1, 2, ATT_NW>(plan.nw, [&](auto nw) {
-            with_bool(plan.early, [&](auto early) {
-                with_bool(packed, [&](auto pk) {
-                    constexpr int NW = decltype(nw)::value;
-                    hipLaunchKernelGGL((attention_h3_kernel<NW, true, decltype(pk)::value, decltype(early)::value>), grid,
-                                       dim3(NW * 64), attention_h3_lds_bytes<NW>(), s, qs, ks, vs, vexp, M, g, opart,
-                                       ml);
-                });
-            });
-        });
-        break;
-    default: return hipErrorInvalidValue;  // ATT_FUSED: launch_attn_pw2
-    }
-    return hipGetLastError();
-}
-
-// fp32 rows [B][N][CH] -> [B][Npad][CH] with zero padding rows (the f32 attention's input)
-__global__ void pad_rows_kernel(const float *__restrict__ x, int B, int N, int Npad, float *__restrict__ y) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)B * Npad * CH) return;
-    const int c = (int)(i % CH), row = (int)((i / CH) % Npad), b = (int)(i / CH / Npad);
-    y[i] = row < N ? x[((size_t)b * N + row) * CH + c] : 0.0f;
-}
-
-hipError_t launch_pad_rows(const float *x, int B, int N, int Npad, float *y, hipStream_t s) {
-    const size_t n = (size_t)B * Npad * CH;
-    hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, B, N, Npad, y);
-    return hipGetLastError();
-}
-
-hipError_t launch_split_qkv(const float *q, const float *k, const float *v, int B, int N, int ld, int Npad,
-                            _Float16 *qs, _Float16 *ks, _Float16 *vs, float *vexp, hipStream_t s) {
-    const size_t n = (size_t)B * Npad * CH;
-    hipLaunchKernelGGL(vexp_kernel, dim3(Npad / H3_TILE, B), dim3(256), 0, s, v, N, ld, Npad, vexp);
-    hipLaunchKernelGGL(split_qkv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, k, v, vexp, B, N, ld,
-                       Npad, qs, ks, vs);
-    return hipGetLastError();
-}
-
-// Combine the split partials of one row segment: msg = sum_s O_s e^{m_s-m*} / sum_s l_s e^{m_s-m*}.
-// Channels d0 .. d0+15 (d0 % 16 == 0) as 4 runs of 4: opart rows [Npad][CH]
-// (F32 attention) or the fragment-block tiling (H3, attention_h3.hpp: run a
-// of the 16 sits in block 2 (d0/16) + (a >> 1), lane half a & 1).
-// Loads are issued in batches (8 maxima, then 4 splits' m, l and 16 channels)
-// before any is used: one L2 round trip per batch instead of one per split
-// (the split loop's loads otherwise wait for each other: 10.6 of a single
-// N = 1000 pair's 25 us pw_mid launch went to the 16-split combine).  Same
-// arithmetic, same order as the one-load-per-split loop.
-#ifndef PDSC_C16_ONE
-#define PDSC_C16_ONE 8  // A/B build knob (-DPDSC_C16_ONE=0: the chunked loads only)
-#endif
-constexpr int C16_ONE = PDSC_C16_ONE;  // combine16: up to this many splits in one batch of loads (r06)
-template <bool F32>
-PDSC_DEV void combine16(const float *__restrict__ opart, const float *__restrict__ ml, int b,
-                        int nsplit, int Npad, int row, int d0, float out[16]) {
-    const float *mlb = ml + ((size_t)b * nsplit * Npad + row) * 2;  // split s: mlb[s * Npad * 2 + {0, 1}]
-    if (nsplit <= C16_ONE) {
-        // every split's m, l and 16 channels in ONE batch of loads (one round
-        // trip to the partials the attention launch just left in other XCDs'
-        // caches, instead of three), the maximum from the loaded m's: the same
-        // operations in the same order as the chunked loop below
-        f32x2 mlv[C16_ONE > 0 ? C16_ONE : 1];
-        f32x4 ov[C16_ONE > 0 ? C16_ONE : 1][4];
-#pragma unroll
-        for (int j = 0; j < C16_ONE; ++j) {
-            if (j < nsplit) {
-                const size_t base = (size_t)(b * nsplit + j) * Npad + row;
-                mlv[j] = *reinterpret_cast<const f32x2 *>(ml + base * 2);
-                const float *ob = opart + (base - row) * CH;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const size_t o = F32 ? (size_t)row * CH + d0 + 4 * i : h3_opart_off(row, d0 + 4 * i);
-                    ov[j][i] = *reinterpret_cast<const f32x4 *>(ob + o);
-                }
-            }
-        }
-        float mstar = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < C16_ONE; ++j)
-            if (j < nsplit) mstar = fmaxf(mstar, mlv[j][0]);
-        float L = 0.0f;
-        f32x4 acc[4] = {};
-#pragma unroll
-        for (int j = 0; j < C16_ONE; ++j) {
-            if (j < nsplit) {
-                const float w = expf(mlv[j][0] - mstar);
-                L += w * mlv[j][1];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] += w * ov[j][i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[4 * i + e] = acc[i][e] / L;
-        return;
-    }
-    float mstar = -INFINITY;
-    for (int s0 = 0; s0 < nsplit; s0 += 8) {
-        float mv[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mv[j] = s0 + j < nsplit ? mlb[(size_t)(s0 + j) * Npad * 2] : -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mstar = fmaxf(mstar, mv[j]);
-    }
-    float L = 0.0f;
-    f32x4 acc[4] = {};
-    constexpr int SB = 4;
-    for (int s0 = 0; s0 < nsplit; s0 += SB) {
-        f32x2 mlv[SB];
-        f32x4 ov[SB][4];
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            if (s0 + j < nsplit) {
-                const size_t base = (size_t)(b * nsplit + s0 + j) * Npad + row;
-                mlv[j] = *reinterpret_cast<const f32x2 *>(ml + base * 2);
-                const float *ob = opart + (base - row) * CH;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const size_t o = F32 ? (size_t)row * CH + d0 + 4 * i : h3_opart_off(row, d0 + 4 * i);
-                    ov[j][i] = *reinterpret_cast<const f32x4 *>(ob + o);
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            if (s0 + j < nsplit) {
-                const float w = expf(mlv[j][0] - mstar);
-                L += w * mlv[j][1];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] += w * ov[j][i];
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) out[4 * i + e] = acc[i][e] / L;
-}
-
+// The standalone attention's combine (attention.hip calls it).  It is compiled here, beside the pointwise
+// kernels that inline the same combine16: in attention.hip the compiler allocates the kernel's registers
+// differently (same resources, another instruction stream), and no kernel's code may move.
 template <bool F32>
 __global__ __launch_bounds__(256) void attn_combine_kernel(const float *__restrict__ opart,
                                                            const float *__restrict__ ml, int N,
@@ -585,708 +270,11 @@ __global__ __launch_bounds__(256) void combine_rows_kernel(const float *__restri
     if (d0 == 0) *reinterpret_cast<f32x2 *>(ml1 + (base1 + row) * 2) = f32x2{0.0f, 1.0f};
 }
 
-hipError_t launch_combine_rows(const float *opart, const float *ml, int B, int Npad, int nsplit, float *opart1,
+static hipError_t launch_combine_rows(const float *opart, const float *ml, int B, int Npad, int nsplit, float *opart1,
                                float *ml1, hipStream_t s) {
     hipLaunchKernelGGL(combine_rows_kernel, dim3((Npad + 7) / 8, B), dim3(256), 0, s, opart, ml, nsplit, Npad, opart1,
                        ml1);
     return hipGetLastError();
-}
-
-// ============================================================ pointwise chain
-// A workgroup (4 waves) owns PT = 64 points (two 32-row MFMA tiles) held in LDS
-// and runs the whole per-point chain between two attention launches.
-// Dense layer Y = epi(X W^T + b): A operand = X rows (lane -> point), B operand
-// = packed W (one coalesced 1-KiB load per 4 MFMAs).  Wide layers (>= 128
-// outputs): each wave owns column tiles and computes BOTH row tiles, so every
-// weight fragment feeds two MFMAs; narrow layers (32/64 outputs): one
-// (row tile, column tile) per wave so all four waves stay busy.
-enum Epi { EPI_BIAS = 0, EPI_RELU = 1, EPI_BN_RELU = 2, EPI_RESID = 3, EPI_RESID_R = 4 };
-
-// ReLU that keeps NaN (torch.relu(nan) = nan; fmaxf(nan, 0) = 0).  The fp16
-// range guard relies on it: a 3xfp16 operand beyond fp16's range (hi = inf,
-// lo = -inf) makes its contraction NaN, and this carries the NaN on to the
-// logits, where select_best_kernel flags the pair (pdsc.h, PDSC_ERR_RANGE)
-// instead of a ReLU silently zeroing it.  Same value as fmaxf(x, 0) for every
-// non-NaN x (-0 -> +0).  IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950.
-PDSC_DEV float relu_nan(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
-
-constexpr int S132 = CH + 4, S68 = CH2 + 4, S36 = CLS + 4;
-constexpr int IN_MAX = 16;     // layer0 input width held in registers (pw_first)
-constexpr int IN_LIMIT = 128;  // layer0 input width supported (datasets/ThreeDMatch.py:311-315: 70)
-
-// The wave's weight panel for output tile ct.  H3: per 16-input k-step, the hi
-// and lo fragments (lane (h, n): inputs 16 ks + 8h .. +7 of output 32 ct + n).
-// F32: per 8-input chunk j, lane (h, n) holds inputs 8j + 4h .. +3 of output
-// 32 ct + n -- the exact-fp32 MFMA's k-step 4j + e uses input 8j + 4h + e (the
-// activations are read with the same map, so the products pair up).
-template <int IN, bool F32> struct WPanel;
-template <int IN> struct WPanel<IN, false> {
-    f16x8 h[IN / 16], m[IN / 16], l[W_PLANES == 3 ? IN / 16 : 1];  // (l: the 3-plane build only)
-};
-template <int IN> struct WPanel<IN, true> {
-    f32x4 w[IN / 8];
-};
-
-template <int IN, int OUT, bool F32>
-PDSC_DEV void load_wpanel(const float *__restrict__ pk, const DenseOff &off, int ct, int lane, WPanel<IN, F32> &p) {
-    if constexpr (F32) {
-        const float *W = pk + off.w;
-        const size_t rowo = (size_t)(ct * 32 + (lane & 31)) * IN + 4 * (lane >> 5);
-#pragma unroll
-        for (int j = 0; j < IN / 8; ++j) p.w[j] = *reinterpret_cast<const f32x4 *>(W + rowo + 8 * j);
-    } else {
-        const _Float16 *W = reinterpret_cast<const _Float16 *>(pk + off.w) + (size_t)ct * (IN / 16) * W3_BLOCK + 8 * lane;
-#pragma unroll
-        for (int ks = 0; ks < IN / 16; ++ks) {
-            p.h[ks] = *reinterpret_cast<const f16x8 *>(W + ks * W3_BLOCK);
-            p.m[ks] = *reinterpret_cast<const f16x8 *>(W + ks * W3_BLOCK + 512);
-            if constexpr (W_PLANES == 3) p.l[ks] = *reinterpret_cast<const f16x8 *>(W + ks * W3_BLOCK + 1024);
-        }
-    }
-}
-
-// The 8 fp32 activations at positions 8h .. 8h+7 of the k-step starting at x
-// (qk_pos order: channels 4h..4h+3 and 8+4h..8+4h+3; LDS, 16-B aligned) ->
-// hi / lo fp16 fragments.
-PDSC_DEV void split8(const float *x, int h, f16x8 &hi, f16x8 &lo) {
-    const f32x4 a = *reinterpret_cast<const f32x4 *>(x + 4 * h), b = *reinterpret_cast<const f32x4 *>(x + 8 + 4 * h);
-    const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    split8x(v, hi, lo);
-}
-
-// One 32-output tile of Y = epi(X W^T + b) for NRT row tiles.  H3: the fp16
-// matrix cores with the 3-product split (attention_h3.hpp), activations split
-// as they are read from LDS, weights pre-split and pre-scaled by 2^s (the
-// accumulator is scaled back by the exact 2^-s before the bias).  F32: exact
-// fp32 MFMA 32x32x2 on the fp32 activations and weights.
-template <int IN, int OUT, int EPI, int NRT, bool F32>
-PDSC_DEV void dense_tile_w(const float *X, int xstr, const WPanel<IN, F32> &wp, const float *__restrict__ pk,
-                           const DenseOff &off, int rt0, int ct, float *Y, int ystr, const float *__restrict__ resid,
-                           int lane, const float *rres = nullptr) {
-    const int h = lane >> 5, l32 = lane & 31;
-    f32x16 acc[NRT];
-#pragma unroll
-    for (int i = 0; i < NRT; ++i) acc[i] = zero16();
-    if constexpr (F32) {
-        const float *xp = X + (rt0 * 32 + l32) * xstr + 4 * h;
-#pragma unroll
-        for (int j = 0; j < IN / 8; ++j) {
-#pragma unroll
-            for (int i = 0; i < NRT; ++i) {
-                const f32x4 xv = *reinterpret_cast<const f32x4 *>(xp + i * 32 * xstr + 8 * j);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i] = mfma32(xv[e], wp.w[j][e], acc[i]);
-            }
-        }
-    } else {
-        const float *xp = X + (rt0 * 32 + l32) * xstr;
-#pragma unroll
-        for (int ks = 0; ks < IN / 16; ++ks) {
-#pragma unroll
-            for (int i = 0; i < NRT; ++i) {
-                f16x8 xh, xl;
-                split8(xp + i * 32 * xstr + 16 * ks, h, xh, xl);
-                acc[i] = mfma_xw3(xh, xl, wp.h[ks], wp.m[ks], wp.l[W_PLANES == 3 ? ks : 0], acc[i]);
-            }
-        }
-    }
-    const int j = ct * 32 + l32;
-    const float inv = pk[off.scale];
-    const float bias = pk[off.bias + j];
-    const float al = pk[off.alpha + j], be = pk[off.beta + j];
-#pragma unroll
-    for (int i = 0; i < NRT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (rt0 + i) * 32 + acc_row(r, h);
-            float y = acc[i][r] * inv + bias;
-            if (EPI == EPI_BN_RELU) y = relu_nan(y * al + be);  // eval BN as torch folds it, ReLU
-            if (EPI == EPI_RELU) y = relu_nan(y);
-            if (EPI == EPI_RESID) y = resid[row * CH + j] + y;      // res = feat + message (:44)
-            if (EPI == EPI_RESID_R) y = rres[16 * i + r] + y;       // the same, rows loaded ahead (NRT = 1)
-            Y[row * ystr + j] = y;
-        }
-}
-
-template <int IN, int OUT, int EPI, int NRT, bool F32>
-PDSC_DEV void dense_tile(const float *X, int xstr, const float *__restrict__ pk, const DenseOff &off,
-                         int rt0, int ct, float *Y, int ystr, const float *__restrict__ resid, int lane) {
-    WPanel<IN, F32> wp;  // the wave's whole weight panel, issued up front
-    load_wpanel<IN, OUT, F32>(pk, off, ct, lane, wp);
-    // keep the scheduler from sinking the loads next to their uses (each would
-    // then expose a full L2 round trip per k-step); waits stay counted
-    asm volatile("" ::: "memory");
-    dense_tile_w<IN, OUT, EPI, NRT, F32>(X, xstr, wp, pk, off, rt0, ct, Y, ystr, resid, lane);
-}
-
-// Q/K/V projections (Conv1d 128 -> 128 + bias, :36-38) of the PT-point tile,
-// written as fp16 hi/lo splits in the attention_h3 layouts.  Wave `ct` owns
-// output channels ct*32..+31 of both 32-point row tiles.
-//   SPLIT_Q, SPLIT_K: transposed product (accumulator rows = channels, lane =
-//     point), so registers 8s..8s+7 are 8 consecutive qk_pos positions: one
-//     16-B store of hi and one of lo per (row tile, s); K chunks swizzled.
-//   SPLIT_V: lane = channel, registers 8s..8s+7 = 8 consecutive v_keypos
-//     positions of the point tile: 16-B stores into the tile's V planes.
-enum SplitMode { SPLIT_Q = 0, SPLIT_K = 1, SPLIT_V = 2 };
-
-// The PT x 128 activation tile split once into hi / lo fp16 in LDS (row r:
-// 16 hi chunks of 16 B then 16 lo chunks, chunk c stored at c ^ (r & 15) so a
-// fragment read -- 32 rows, one chunk each -- is conflict-free).  Shared by the
-// Q, K and V products instead of re-splitting per wave and per product.
-constexpr int XS_ROWB = 2 * CH * 2;  // bytes per split row
-template <int PTT, int NT = 256>
-PDSC_DEV void split_tile(const float *X, int xstr, char *Xs, int tid) {
-    constexpr int TPR = NT / PTT, CPT = 16 / TPR;  // threads per row, chunks per thread
-    const int r = tid / TPR;
-#pragma unroll
-    for (int q = 0; q < CPT; ++q) {
-        const int c = (tid % TPR) * CPT + q;  // chunk c = positions 8c .. 8c+7 (qk_pos order)
-        f16x8 hi, lo;
-        split8(X + r * xstr + 16 * (c >> 1), c & 1, hi, lo);
-        const int o = r * XS_ROWB + 16 * (c ^ (r & 15));
-        *reinterpret_cast<f16x8 *>(Xs + o) = hi;
-        *reinterpret_cast<f16x8 *>(Xs + o + CH * 2) = lo;
-    }
-}
-
-// SPLIT_V also sets the tile exponents vexp[p0/32 + i] (attention_h3.hpp) from
-// the max |v| over the 4 waves' channel tiles, exchanged through `red` (LDS,
-// 4 * NRT floats no other wave reads at this point; one barrier).
-// active = false (8-wave workgroups, SPLIT_V): the wave only joins the barrier.
-template <int MODE, int NRT>
-PDSC_DEV void dense_split(const char *Xs, const WPanel<CH, false> &wp, const float *__restrict__ pk,
-                          const DenseOff &off, int ct, _Float16 *__restrict__ dst, int p0, int lane,
-                          float *red = nullptr, float *__restrict__ vexp = nullptr, bool active = true) {
-    const int h = lane >> 5, l32 = lane & 31;
-    f32x16 acc[NRT];
-#pragma unroll
-    for (int i = 0; i < NRT; ++i) acc[i] = zero16();
-    if (active)
-#pragma unroll
-    for (int ks = 0; ks < CH / 16; ++ks) {
-#pragma unroll
-        for (int i = 0; i < NRT; ++i) {
-            const int r = 32 * i + l32;
-            const char *xr = Xs + r * XS_ROWB + 16 * ((2 * ks + h) ^ (r & 15));
-            const f16x8 xh = *reinterpret_cast<const f16x8 *>(xr);
-            const f16x8 xl = *reinterpret_cast<const f16x8 *>(xr + CH * 2);
-            acc[i] = MODE == SPLIT_V ? mfma_xw3(xh, xl, wp.h[ks], wp.m[ks], wp.l[W_PLANES == 3 ? ks : 0], acc[i])
-                                     : mfma_w3x(wp.h[ks], wp.m[ks], wp.l[W_PLANES == 3 ? ks : 0], xh, xl, acc[i]);
-        }
-    }
-    const float inv = pk[off.scale];
-    if constexpr (MODE == SPLIT_V) {
-        const int c = ct * 32 + l32;
-        const float bias = pk[off.bias + c];
-        int ev[NRT];
-        if (active)
-#pragma unroll
-        for (int i = 0; i < NRT; ++i) {
-            float m = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                acc[i][r] = acc[i][r] * inv + bias;
-                m = fmaxf(m, fabsf(acc[i][r]));
-            }
-            m = wave_max(m);
-            if (lane == 0) red[4 * i + ct] = m;
-        }
-        __syncthreads();
-        if (!active) return;
-#pragma unroll
-        for (int i = 0; i < NRT; ++i) {
-            ev[i] = h3_vexp(fmaxf(fmaxf(red[4 * i], red[4 * i + 1]), fmaxf(red[4 * i + 2], red[4 * i + 3])));
-            if (ct == 0 && lane == 0) vexp[(p0 >> 5) + i] = (float)ev[i];
-        }
-#pragma unroll
-        for (int i = 0; i < NRT; ++i) {
-            _Float16 *tile = dst + (size_t)((p0 >> 5) + i) * H3_TILE_H;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                f16x8 hi, lo;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    _Float16 a, b;
-                    split_h(ldexpf(acc[i][8 * s + e], ev[i]), a, b);
-                    hi[e] = a;
-                    lo[e] = b;
-                }
-                *reinterpret_cast<f16x8 *>(tile + h3_frag(2 * ct + s, 0, lane)) = hi;
-                *reinterpret_cast<f16x8 *>(tile + h3_frag(2 * ct + s, 1, lane)) = lo;
-            }
-        }
-    } else {
-        float bias[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bias[r] = pk[off.bias + ct * 32 + acc_row(r, h)];
-#pragma unroll
-        for (int i = 0; i < NRT; ++i) {
-            _Float16 *tile = dst + (size_t)((p0 >> 5) + i) * H3_TILE_H;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                f16x8 hi, lo;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    _Float16 a, b;
-                    const float y = acc[i][8 * s + e] * inv + bias[8 * s + e];
-                    split_h(MODE == SPLIT_Q && ATT_QFMA ? y * H3_QSCALE : y, a, b);
-                    hi[e] = a;
-                    lo[e] = b;
-                }
-                *reinterpret_cast<f16x8 *>(tile + h3_frag(2 * ct + s, 0, lane)) = hi;
-                *reinterpret_cast<f16x8 *>(tile + h3_frag(2 * ct + s, 1, lane)) = lo;
-            }
-        }
-    }
-}
-
-// Y = epi(X W^T + b) over a PTT-point tile (PTT/32 row tiles) by 4 waves.
-template <int IN, int OUT, int EPI, int PTT, bool F32, int NWV = 4>
-PDSC_DEV void dense64(const float *X, int xstr, const float *__restrict__ pk, const DenseOff &off, float *Y,
-                      int ystr, const float *__restrict__ resid, int wave, int lane) {
-    constexpr int NCT = OUT / 32, NRT = PTT / 32;
-    static_assert(NWV == 4 || NRT == 1, "8-wave workgroups take 32-point tiles");
-    if constexpr (NCT >= 4) {
-        for (int ct = wave; ct < NCT; ct += NWV)
-            dense_tile<IN, OUT, EPI, NRT, F32>(X, xstr, pk, off, 0, ct, Y, ystr, resid, lane);
-    } else if constexpr (NRT == 2) {
-        const int rt = wave & 1, ct = wave >> 1;
-        if (ct < NCT) dense_tile<IN, OUT, EPI, 1, F32>(X, xstr, pk, off, rt, ct, Y, ystr, resid, lane);
-    } else {
-        if (wave < NCT) dense_tile<IN, OUT, EPI, 1, F32>(X, xstr, pk, off, 0, wave, Y, ystr, resid, lane);
-    }
-}
-
-// Copy a [PT][CH] LDS tile (stride xstr) to global rows [p0, p0 + nrows) (row stride CH).
-template <int PTT, int NT = 256>
-PDSC_DEV void store_rows(const float *X, int xstr, float *__restrict__ dst, int p0, int nrows, int tid) {
-    for (int e = tid; e < PTT * (CH / 4); e += NT) {
-        const int p = e / (CH / 4), c4 = e % (CH / 4);
-        if (p < nrows)
-            *reinterpret_cast<f32x4 *>(dst + (size_t)(p0 + p) * CH + 4 * c4) =
-                *reinterpret_cast<const f32x4 *>(X + p * xstr + 4 * c4);
-    }
-}
-
-struct PwDense4 {  // PointCN + Q/K/V of one layer
-    DenseOff pcn, q, k, v;
-};
-struct PwMsg {  // fc_message of one layer
-    DenseOff fc0, fc3, fc6;
-};
-
-// LDS: A, B = [PT][S132] (67,584 B -> 2 workgroups per CU).  The fc_message
-// hidden tile C [PT][S68] and pw_first's corr_pos tile live in B, which is free
-// until the residual add writes it.
-template <int PTT> constexpr size_t pw_lds() { return (size_t)(2 * PTT * S132) * sizeof(float); }
-
-// PointCN_l (Xin -> Xout) then Q/K/V_l (Xout -> the attention's input layouts);
-// Xout rows -> feat.  Q, K, V point at the pair's buffers: the fp16 hi/lo split
-// layouts (H3) or fp32 [Npad][CH] rows (F32, same bytes).
-// only = 0 / 1 / 2 (H3): this workgroup writes Q / K / V alone (feat only with
-// Q), as pcn_qkv8's `only` (pw_first_kernel's z dimension).
-template <int PTT, bool F32>
-PDSC_DEV void pcn_qkv(const float *Xin, float *Xout, const float *__restrict__ pk, const PwDense4 &d,
-                      float *__restrict__ feat, _Float16 *__restrict__ Q, _Float16 *__restrict__ K,
-                      _Float16 *__restrict__ V, float *__restrict__ vexp, int p0, int tid, int wave, int lane,
-                      int only = -1) {
-    // four 128 -> 128 products with the same wave -> output-tile map (ct = wave):
-    // each one's weight panel is fetched while the previous one computes
-    WPanel<CH, F32> pa, pb;
-    if constexpr (!F32) {
-        if (only >= 0) {  // workgroup-uniform
-            load_wpanel<CH, CH, F32>(pk, d.pcn, wave, lane, pa);
-            load_wpanel<CH, CH, F32>(pk, only == 0 ? d.q : (only == 1 ? d.k : d.v), wave, lane, pb);
-            asm volatile("" ::: "memory");
-            dense_tile_w<CH, CH, EPI_BN_RELU, PTT / 32, F32>(Xin, S132, pa, pk, d.pcn, 0, wave, Xout, S132, nullptr,
-                                                             lane);
-            __syncthreads();  // Xout complete; Xin is dead (it now holds the split copy of Xout)
-            char *Xs = reinterpret_cast<char *>(const_cast<float *>(Xin));
-            split_tile<PTT>(Xout, S132, Xs, tid);
-            if (only == 0) store_rows<PTT>(Xout, S132, feat, p0, PTT, tid);
-            __syncthreads();
-            if (only == 0)
-                dense_split<SPLIT_Q, PTT / 32>(Xs, pb, pk, d.q, wave, Q, p0, lane);
-            else if (only == 1)
-                dense_split<SPLIT_K, PTT / 32>(Xs, pb, pk, d.k, wave, K, p0, lane);
-            else
-                dense_split<SPLIT_V, PTT / 32>(Xs, pb, pk, d.v, wave, V, p0, lane, Xout, vexp);  // Xout is dead
-            return;
-        }
-    }
-    load_wpanel<CH, CH, F32>(pk, d.pcn, wave, lane, pa);
-    load_wpanel<CH, CH, F32>(pk, d.q, wave, lane, pb);
-    asm volatile("" ::: "memory");
-    dense_tile_w<CH, CH, EPI_BN_RELU, PTT / 32, F32>(Xin, S132, pa, pk, d.pcn, 0, wave, Xout, S132, nullptr, lane);
-    __syncthreads();  // Xout complete; Xin is dead (H3: it now holds the split copy of Xout)
-    CH_STAMP(155);
-    if constexpr (F32) {
-        float *Qf = reinterpret_cast<float *>(Q) + (size_t)p0 * CH, *Kf = reinterpret_cast<float *>(K) + (size_t)p0 * CH,
-              *Vf = reinterpret_cast<float *>(V) + (size_t)p0 * CH;
-        load_wpanel<CH, CH, F32>(pk, d.k, wave, lane, pa);
-        asm volatile("" ::: "memory");
-        store_rows<PTT>(Xout, S132, feat, p0, PTT, tid);
-        dense_tile_w<CH, CH, EPI_BIAS, PTT / 32, F32>(Xout, S132, pb, pk, d.q, 0, wave, Qf, CH, nullptr, lane);
-        load_wpanel<CH, CH, F32>(pk, d.v, wave, lane, pb);
-        asm volatile("" ::: "memory");
-        dense_tile_w<CH, CH, EPI_BIAS, PTT / 32, F32>(Xout, S132, pa, pk, d.k, 0, wave, Kf, CH, nullptr, lane);
-        dense_tile_w<CH, CH, EPI_BIAS, PTT / 32, F32>(Xout, S132, pb, pk, d.v, 0, wave, Vf, CH, nullptr, lane);
-    } else {
-        char *Xs = reinterpret_cast<char *>(const_cast<float *>(Xin));
-        split_tile<PTT>(Xout, S132, Xs, tid);
-        load_wpanel<CH, CH, F32>(pk, d.k, wave, lane, pa);
-        asm volatile("" ::: "memory");
-        store_rows<PTT>(Xout, S132, feat, p0, PTT, tid);
-        __syncthreads();
-        CH_STAMP(156);
-        dense_split<SPLIT_Q, PTT / 32>(Xs, pb, pk, d.q, wave, Q, p0, lane);
-        load_wpanel<CH, CH, F32>(pk, d.v, wave, lane, pb);
-        asm volatile("" ::: "memory");
-        CH_STAMP(157);
-        dense_split<SPLIT_K, PTT / 32>(Xs, pa, pk, d.k, wave, K, p0, lane);
-        CH_STAMP(158);
-        dense_split<SPLIT_V, PTT / 32>(Xs, pb, pk, d.v, wave, V, p0, lane, Xout, vexp);  // Xout is dead
-        CH_STAMP(159);
-    }
-}
-
-// pcn_qkv for 8-wave workgroups (H3, 32-point tiles; small batches): PointCN on
-// waves 0-3, then Q (waves 0-3) and K (waves 4-7) at once, then V (waves 0-3).
-// Every output tile is the same dense_tile_w / dense_split code as the 4-wave
-// form, so the same bits.  only = 0 / 1 / 2: this workgroup writes Q / K / V
-// alone (and feat only for Q): three workgroups per point tile share the
-// projections (pw_mid_kernel's z dimension), each streaming 4 of the chain's
-// 7 weight panels instead of all 7 -- the single pair's chain is bound by
-// each CU streaming its panels.
-template <int PTT>
-PDSC_DEV void pcn_qkv8(const float *Xin, float *Xout, const float *__restrict__ pk, const PwDense4 &d,
-                       float *__restrict__ feat, _Float16 *__restrict__ Q, _Float16 *__restrict__ K,
-                       _Float16 *__restrict__ V, float *__restrict__ vexp, int p0, int tid, int wave, int lane,
-                       int only = -1) {
-    static_assert(PTT == 32, "8-wave chain: 32-point tiles");
-    const int w4 = wave & 3;
-    const bool lo = wave < 4;
-    WPanel<CH, false> pa, pb;
-    if (only >= 0) {  // workgroup-uniform
-        if (lo) {
-            load_wpanel<CH, CH, false>(pk, d.pcn, w4, lane, pa);
-            load_wpanel<CH, CH, false>(pk, only == 0 ? d.q : (only == 1 ? d.k : d.v), w4, lane, pb);
-        }
-        asm volatile("" ::: "memory");
-        if (lo) dense_tile_w<CH, CH, EPI_BN_RELU, 1, false>(Xin, S132, pa, pk, d.pcn, 0, w4, Xout, S132, nullptr, lane);
-        __syncthreads();  // Xout complete; Xin is dead (it now holds the split copy of Xout)
-        CH_STAMP(155);
-        char *Xs = reinterpret_cast<char *>(const_cast<float *>(Xin));
-        split_tile<PTT, 512>(Xout, S132, Xs, tid);
-        if (only == 0) store_rows<PTT, 512>(Xout, S132, feat, p0, PTT, tid);
-        __syncthreads();
-        CH_STAMP(156);
-        CH_STAMP(157);
-        CH_STAMP(158);
-        if (only == 0) {
-            if (lo) dense_split<SPLIT_Q, 1>(Xs, pb, pk, d.q, w4, Q, p0, lane);
-        } else if (only == 1) {
-            if (lo) dense_split<SPLIT_K, 1>(Xs, pb, pk, d.k, w4, K, p0, lane);
-        } else {
-            dense_split<SPLIT_V, 1>(Xs, pb, pk, d.v, w4, V, p0, lane, Xout, vexp, lo);  // Xout is dead
-        }
-        CH_STAMP(159);
-        return;
-    }
-    if (lo) {
-        load_wpanel<CH, CH, false>(pk, d.pcn, w4, lane, pa);
-        load_wpanel<CH, CH, false>(pk, d.q, w4, lane, pb);
-    } else {
-        load_wpanel<CH, CH, false>(pk, d.k, w4, lane, pb);
-    }
-    asm volatile("" ::: "memory");
-    if (lo) dense_tile_w<CH, CH, EPI_BN_RELU, 1, false>(Xin, S132, pa, pk, d.pcn, 0, w4, Xout, S132, nullptr, lane);
-    __syncthreads();  // Xout complete; Xin is dead (it now holds the split copy of Xout)
-    CH_STAMP(155);
-    char *Xs = reinterpret_cast<char *>(const_cast<float *>(Xin));
-    split_tile<PTT, 512>(Xout, S132, Xs, tid);
-    if (lo) load_wpanel<CH, CH, false>(pk, d.v, w4, lane, pa);
-    asm volatile("" ::: "memory");
-    store_rows<PTT, 512>(Xout, S132, feat, p0, PTT, tid);
-    __syncthreads();
-    CH_STAMP(156);
-    CH_STAMP(157);  // (Q and K run at once: the "k" phase of tools/pw_stamps.py)
-    if (lo)
-        dense_split<SPLIT_Q, 1>(Xs, pb, pk, d.q, w4, Q, p0, lane);
-    else
-        dense_split<SPLIT_K, 1>(Xs, pb, pk, d.k, w4, K, p0, lane);
-    CH_STAMP(158);
-    dense_split<SPLIT_V, 1>(Xs, pa, pk, d.v, w4, V, p0, lane, Xout, vexp, lo);  // Xout is dead
-    CH_STAMP(159);
-}
-
-// layer0 (Conv1d in_dim -> 128, :54, :73) + PointCN_0 + QKV_0.
-template <int PTT, bool F32>
-__global__ __launch_bounds__(256, 2) void pw_first_kernel(const float *__restrict__ pk, size_t l0w,
-                                                       size_t l0b, PwDense4 d,
-                                                       const float *__restrict__ corr, int in_dim,
-                                                       int N, int Npad, float *__restrict__ feat,
-                                                       _Float16 *__restrict__ Q, _Float16 *__restrict__ K,
-                                                       _Float16 *__restrict__ V, float *__restrict__ vexp,
-                                                       const int *__restrict__ nv) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *XA = sm, *XB = sm + PTT * S132, *cp = XB;  // cp: [PTT][in_dim], consumed before XB is written
-    const int b = blockIdx.y, p0 = blockIdx.x * PTT;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const size_t boff = (size_t)b * Npad * CH;
-    const int n = nv ? nv[b] : N;  // this pair's rows (ragged batches); N: the row stride
-    for (int e = tid; e < PTT * in_dim; e += 256) {
-        const int p = e / in_dim;
-        cp[e] = (p0 + p < n) ? corr[((size_t)b * N + p0) * in_dim + e] : 0.0f;
-    }
-    // thread -> output channel j (both halves of the block cover rows of opposite parity)
-    const int j = tid & (CH - 1), p_off = tid >> 7;
-    const float bj = pk[l0b + j];
-    if (in_dim <= IN_MAX) {  // the weights in registers
-        float w[IN_MAX];
-#pragma unroll
-        for (int c = 0; c < IN_MAX; ++c) w[c] = (c < in_dim) ? pk[l0w + j * in_dim + c] : 0.0f;
-        __syncthreads();
-        for (int p = p_off; p < PTT; p += 2) {
-            float s = 0.0f;
-#pragma unroll
-            for (int c = 0; c < IN_MAX; ++c)
-                if (c < in_dim) s = __builtin_fmaf(w[c], cp[p * in_dim + c], s);
-            XA[p * S132 + j] = s + bj;
-        }
-    } else {  // wide inputs (in_dim <= IN_LIMIT): the same ascending fma chain, weights from L1
-        __syncthreads();
-        const float *wj = pk + l0w + (size_t)j * in_dim;
-        for (int p = p_off; p < PTT; p += 2) {
-            float s = 0.0f;
-            for (int c = 0; c < in_dim; ++c) s = __builtin_fmaf(wj[c], cp[p * in_dim + c], s);
-            XA[p * S132 + j] = s + bj;
-        }
-    }
-    __syncthreads();
-    pcn_qkv<PTT, F32>(XA, XB, pk, d, feat + boff, Q + 2 * boff, K + 2 * boff, V + 2 * boff,
-                      vexp + (size_t)b * (Npad / 32), p0, tid, wave, lane, gridDim.z == 3 ? (int)blockIdx.z : -1);
-}
-
-// Combine the split partials of rows p0..p0+63 into X (stride S132); 4 threads per row.
-template <int PTT, bool F32>
-PDSC_DEV void combine_tile(const float *__restrict__ opart, const float *__restrict__ ml, int b,
-                           int nsplit, int Npad, int p0, float *X, int tid) {
-    constexpr int TPR = 256 / PTT, NH = 8 / TPR;  // threads per row, 16-channel pieces per thread
-    const int p = tid / TPR;
-#pragma unroll
-    for (int half = 0; half < NH; ++half) {
-        const int d0 = (tid % TPR) * (16 * NH) + half * 16;
-        float out[16];
-        combine16<F32>(opart, ml, b, nsplit, Npad, p0 + p, d0, out);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            *reinterpret_cast<f32x4 *>(X + p * S132 + d0 + 4 * i) =
-                f32x4{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
-    }
-}
-
-// fc_message + residual (:43-44): X = msg (A) -> C -> A (stride S68) -> R (B);
-// C may alias R: it is dead once fc3 has read it (barrier before fc6).
-template <int PTT, bool F32, int NWV = 4>
-PDSC_DEV void message_resid(float *A, float *C, float *R, const float *__restrict__ pk, const PwMsg &m,
-                            const float *__restrict__ feat_rows, int wave, int lane) {
-    dense64<CH, CH2, EPI_BN_RELU, PTT, F32, NWV>(A, S132, pk, m.fc0, C, S68, nullptr, wave, lane);
-    __syncthreads();
-    CH_STAMP(152);
-    dense64<CH2, CH2, EPI_BN_RELU, PTT, F32, NWV>(C, S68, pk, m.fc3, A, S68, nullptr, wave, lane);
-    __syncthreads();
-    CH_STAMP(153);
-    dense64<CH2, CH, EPI_RESID, PTT, F32, NWV>(A, S68, pk, m.fc6, R, S132, feat_rows, wave, lane);
-    __syncthreads();
-    CH_STAMP(154);
-}
-
-// pw_mid's chain for the 8-wave workgroups of a Q / K / V split (three
-// workgroups per 32-point tile, `only` = blockIdx.z), each wave's weight panel
-// loaded a phase ahead of its layer instead of at its start (the single pair's
-// chain is a sequence of L2 round trips: every layer of the message chain paid
-// one before its MFMAs).  Roles: fc0 on waves 4-5 and fc3 on waves 6-7 (panels
-// loaded before the combine), fc6 on waves 0-3 (panel and residual rows loaded
-// before the combine), PointCN on waves 4-7 (panel loaded once fc0 / fc3 are
-// done, during fc6), the projection on waves 0-3 (panel loaded after fc6,
-// during PointCN).  Every output tile is the same dense_tile_w / dense_split
-// arithmetic as message_resid + pcn_qkv8: the same bits.
-PDSC_DEV void mid_split8(float *XA, float *XB, const float *__restrict__ pk, const PwMsg &m, const PwDense4 &d,
-                         const float *__restrict__ opart, const float *__restrict__ ml, int b, int nsplit, int Npad,
-                         int p0, const float *__restrict__ feat_rows, float *__restrict__ feat,
-                         _Float16 *__restrict__ Q, _Float16 *__restrict__ K, _Float16 *__restrict__ V,
-                         float *__restrict__ vexp, int only, int tid, int wave, int lane) {
-    constexpr int PTT = 32;
-    float *XC = XB;
-    const int w4 = wave & 3, h = lane >> 5, l32 = lane & 31;
-    WPanel<CH, false> pa;   // fc0 (waves 4-5), then PointCN (waves 4-7) / the projection (waves 0-3)
-    WPanel<CH2, false> pb;  // fc3 (waves 6-7) / fc6 (waves 0-3)
-    float res[16];          // fc6's residual rows (waves 0-3)
-    if (wave >= 6)
-        load_wpanel<CH2, CH2, false>(pk, m.fc3, wave - 6, lane, pb);
-    else if (wave >= 4)
-        load_wpanel<CH, CH2, false>(pk, m.fc0, wave - 4, lane, pa);
-    asm volatile("" ::: "memory");
-    if (tid < 256) {
-        combine_tile<PTT, false>(opart, ml, b, nsplit, Npad, p0, XA, tid);
-        // (after the combine: its loads and these do not share the register file)
-        load_wpanel<CH2, CH, false>(pk, m.fc6, wave, lane, pb);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) res[r] = feat_rows[acc_row(r, h) * CH + wave * 32 + l32];
-    }
-    asm volatile("" ::: "memory");
-    __syncthreads();
-    CH_STAMP(151);
-    if (wave == 4 || wave == 5)  // fc0: XA -> XC
-        dense_tile_w<CH, CH2, EPI_BN_RELU, 1, false>(XA, S132, pa, pk, m.fc0, 0, wave - 4, XC, S68, nullptr, lane);
-    __syncthreads();
-    CH_STAMP(152);
-    if (wave >= 4) load_wpanel<CH, CH, false>(pk, d.pcn, w4, lane, pa);  // (waves 4-5 are done with fc0's)
-    asm volatile("" ::: "memory");
-    if (wave >= 6)  // fc3: XC -> XA
-        dense_tile_w<CH2, CH2, EPI_BN_RELU, 1, false>(XC, S68, pb, pk, m.fc3, 0, wave - 6, XA, S68, nullptr, lane);
-    __syncthreads();
-    CH_STAMP(153);
-    if (wave < 4)  // fc6 + residual: XA -> XB
-        dense_tile_w<CH2, CH, EPI_RESID_R, 1, false>(XA, S68, pb, pk, m.fc6, 0, wave, XB, S132, nullptr, lane, res);
-    __syncthreads();
-    CH_STAMP(154);
-    if (wave < 4) load_wpanel<CH, CH, false>(pk, only == 0 ? d.q : (only == 1 ? d.k : d.v), wave, lane, pa);
-    asm volatile("" ::: "memory");
-    if (wave >= 4)  // PointCN: XB -> XA
-        dense_tile_w<CH, CH, EPI_BN_RELU, 1, false>(XB, S132, pa, pk, d.pcn, 0, w4, XA, S132, nullptr, lane);
-    __syncthreads();  // XA complete; XB is dead (it now holds the split copy of XA)
-    CH_STAMP(155);
-    char *Xs = reinterpret_cast<char *>(XB);
-    split_tile<PTT, 512>(XA, S132, Xs, tid);
-    if (only == 0) store_rows<PTT, 512>(XA, S132, feat, p0, PTT, tid);
-    __syncthreads();
-    CH_STAMP(156);
-    CH_STAMP(157);
-    CH_STAMP(158);
-    if (only == 0) {
-        if (wave < 4) dense_split<SPLIT_Q, 1>(Xs, pa, pk, d.q, wave, Q, p0, lane);
-    } else if (only == 1) {
-        if (wave < 4) dense_split<SPLIT_K, 1>(Xs, pa, pk, d.k, wave, K, p0, lane);
-    } else {
-        dense_split<SPLIT_V, 1>(Xs, pa, pk, d.v, w4, V, p0, lane, XA, vexp, wave < 4);  // XA is dead
-    }
-    CH_STAMP(159);
-}
-
-template <int PTT, bool F32, int NWV = 4>
-__global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void pw_mid_kernel(const float *__restrict__ pk, PwMsg m, PwDense4 d,
-                                                     const float *__restrict__ opart,
-                                                     const float *__restrict__ ml, int nsplit, int N,
-                                                     int Npad, const float *__restrict__ feat_in,
-                                                     float *__restrict__ feat,
-                                                     _Float16 *__restrict__ Q, _Float16 *__restrict__ K,
-                                                     _Float16 *__restrict__ V, float *__restrict__ vexp,
-                                                     int diag_delay, int prefetch) {
-    // feat_in != feat: with gridDim.z == 3 the three workgroups of a point tile
-    // read feat_in's rows as fc6's residual while the z = 0 one writes feat
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *XA = sm, *XB = sm + PTT * S132, *XC = XB;
-    const int b = blockIdx.y, p0 = blockIdx.x * PTT;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    // diagnostic (PDSC_DIAG_QKV_DELAY, tests only): the K / V workgroups start
-    // late, after the Q one has stored its PointCN rows
-    if (diag_delay > 0 && blockIdx.z != 0)
-        for (int i = 0; i < diag_delay; ++i) __builtin_amdgcn_s_sleep(127);
-    const size_t boff = (size_t)b * Npad * CH;
-#ifdef ATT_STAMPS
-    unsigned long long *stp = att_stamp_ptr(wave);
-    ATT_RSTAMP(stp, 186);
-    ATT_STAMP(stp, 150);
-#endif
-    if constexpr (NWV == 8 && PTT == 32 && !F32) {
-        if (prefetch && gridDim.z == 3) {  // workgroup-uniform
-            mid_split8(XA, XB, pk, m, d, opart, ml, b, nsplit, Npad, p0, feat_in + boff + (size_t)p0 * CH, feat + boff,
-                       Q + 2 * boff, K + 2 * boff, V + 2 * boff, vexp + (size_t)b * (Npad / 32), (int)blockIdx.z, tid,
-                       wave, lane);
-            ATT_RSTAMP(stp, 187);
-            return;
-        }
-    }
-    if (tid < 256) combine_tile<PTT, F32>(opart, ml, b, nsplit, Npad, p0, XA, tid);
-    __syncthreads();
-    ATT_STAMP(stp, 151);
-    message_resid<PTT, F32, NWV>(XA, XC, XB, pk, m, feat_in + boff + (size_t)p0 * CH, wave, lane);
-    if constexpr (NWV == 8)
-        pcn_qkv8<PTT>(XB, XA, pk, d, feat + boff, Q + 2 * boff, K + 2 * boff, V + 2 * boff,
-                      vexp + (size_t)b * (Npad / 32), p0, tid, wave, lane, gridDim.z == 3 ? (int)blockIdx.z : -1);
-    else
-        pcn_qkv<PTT, F32>(XB, XA, pk, d, feat + boff, Q + 2 * boff, K + 2 * boff, V + 2 * boff,
-                          vexp + (size_t)b * (Npad / 32), p0, tid, wave, lane);
-    ATT_RSTAMP(stp, 187);
-}
-
-template <int PTT, bool F32>
-__global__ __launch_bounds__(256, 2) void pw_last_kernel(
-    const float *__restrict__ pk, PwMsg m, DenseOff c0, DenseOff c2, size_t c4w, size_t c4b,
-    const float *__restrict__ opart, const float *__restrict__ ml, int nsplit, int N, int Npad,
-    const float *__restrict__ feat, float *__restrict__ feat_out, float *__restrict__ normed,
-    _Float16 *__restrict__ normed_s, float *__restrict__ conf) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *XA = sm, *XB = sm + PTT * S132, *XC = XB;
-    float *C1 = XA, *C2 = XA + PTT * S36;  // classifier hidden layers reuse A
-    const int b = blockIdx.y, p0 = blockIdx.x * PTT;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const size_t boff = (size_t)b * Npad * CH;
-    const int nrows = min(PTT, N - p0);
-    combine_tile<PTT, F32>(opart, ml, b, nsplit, Npad, p0, XA, tid);
-    __syncthreads();
-    message_resid<PTT, F32>(XA, XC, XB, pk, m, feat + boff + (size_t)p0 * CH, wave, lane);
-    // XB = corr_features rows
-    if (feat_out) store_rows<PTT>(XB, S132, feat_out + (size_t)b * N * CH, p0, nrows, tid);
-    {   // F.normalize(p=2, dim=-1, eps=1e-12) (:156); LPP lanes per point
-        constexpr int LPP = 256 / PTT, CPL = CH / LPP;  // lanes per point, channels per lane
-        const int p = tid / LPP, d0 = (tid % LPP) * CPL;
-        float ss = 0.0f;
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) {
-            const float x = XB[p * S132 + d0 + i];
-            ss = __builtin_fmaf(x, x, ss);
-        }
-#pragma unroll
-        for (int o = 1; o < LPP; o <<= 1) ss += __shfl_xor(ss, o);
-        const float den = fmaxf(sqrtf(ss), 1e-12f);
-        if (p < nrows) {
-            float *dst = normed + ((size_t)b * N + p0 + p) * CH + d0;
-#pragma unroll
-            for (int i = 0; i < CPL / 4; ++i)
-                *reinterpret_cast<f32x4 *>(dst + 4 * i) =
-                    f32x4{XB[p * S132 + d0 + 4 * i] / den, XB[p * S132 + d0 + 4 * i + 1] / den,
-                          XB[p * S132 + d0 + 4 * i + 2] / den, XB[p * S132 + d0 + 4 * i + 3] / den};
-            if (!F32 && normed_s) {  // the fp16 hi/lo split copy (qk_pos order) the H3 seed kNN consumes
-                _Float16 *ds = normed_s + ((size_t)b * N + p0 + p) * 2 * CH;
-#pragma unroll
-                for (int q = 0; q < CPL / 8; ++q) {
-                    f16x8 hi, lo;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        _Float16 a, c;
-                        split_h(XB[p * S132 + qk_pos(d0 + 8 * q + e)] / den, a, c);
-                        hi[e] = a;
-                        lo[e] = c;
-                    }
-                    *reinterpret_cast<f16x8 *>(ds + d0 + 8 * q) = hi;
-                    *reinterpret_cast<f16x8 *>(ds + CH + d0 + 8 * q) = lo;
-                }
-            }
-        }
-    }
-    // classification MLP 128 -> 32 -> 32 -> 1 on the unnormalised features (:171)
-    dense64<CH, CLS, EPI_RELU, PTT, F32>(XB, S132, pk, c0, C1, S36, nullptr, wave, lane);
-    __syncthreads();
-    dense64<CLS, CLS, EPI_RELU, PTT, F32>(C1, S36, pk, c2, C2, S36, nullptr, wave, lane);
-    __syncthreads();
-    if (tid < nrows) {
-        float s = 0.0f;
-        for (int c = 0; c < CLS; ++c) s = __builtin_fmaf(pk[c4w + c], C2[tid * S36 + c], s);
-        conf[(size_t)b * N + p0 + tid] = s + pk[c4b];
-    }
 }
 
 // ============================================== pw2: register-chained pointwise chain
@@ -1495,7 +483,7 @@ PDSC_DEV void w2_epilogue(f32x16 (&acc)[OUT / 32], float inv, const float *cf, c
 
 // Combine the split partials of this lane's point into the k-step fragments of
 // the 128 message channels (as combine16: sum_s w_s O_s / sum_s w_s l_s).  The
-// partials are in the fragment-block tiling (attention_h3.hpp): k-step ks is
+// partials are in the fragment-block tiling (h3.hpp): k-step ks is
 // blocks 2 ks and 2 ks + 1 at this lane, 16 coalesced 1-KiB loads per split.
 PDSC_DEV void w2_combine(const float *__restrict__ opart, const float *__restrict__ ml, int b, int nsplit, int Npad,
                          int row, f16x8 *xh, f16x8 *xl, int lane) {
@@ -2109,7 +1097,7 @@ static PwMsg msg3(const LayerOff &l, bool vfold = false) { return PwMsg{vfold ? 
 
 // The fused launches (the plan's ATT_FUSED): one key split per query block, a
 // workgroup per PW2_PTS queries.
-hipError_t launch_attn_pw2(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
+static hipError_t launch_attn_pw2(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
                            const void *q, const void *k, const void *v, const float *vexp_in, const float *M,
                            float *feat, void *qo, void *ko, void *vo, float *vexp_out, hipStream_t s, Ragged rg) {
     if (!plan.fused() || layer + 1 >= lay.L) return hipErrorInvalidValue;
@@ -2132,7 +1120,7 @@ hipError_t launch_attn_pw2(const EncoderPlan &plan, const float *packed, const P
     return hipGetLastError();
 }
 
-hipError_t launch_attn_pw2_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const void *q,
+static hipError_t launch_attn_pw2_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const void *q,
                                 const void *k, const void *v, const float *vexp_in, const float *M, const float *feat,
                                 float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
                                 Ragged rg) {
@@ -2171,7 +1159,7 @@ hipError_t launch_attn_pw2_last(const EncoderPlan &plan, const float *packed, co
             hipLaunchKernelGGL((K<64, false>), g_, dim3(256), pw_lds<64>(), s, __VA_ARGS__);            \
     } while (0)
 
-hipError_t launch_pw_first(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *corr_pos,
+static hipError_t launch_pw_first(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *corr_pos,
                            float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s, Ragged rg) {
     if (lay.in_dim > IN_LIMIT) return hipErrorInvalidValue;
     const int B = plan.B, N = plan.N, Npad = plan.Npad;
@@ -2197,7 +1185,7 @@ hipError_t launch_pw_first(const EncoderPlan &plan, const float *packed, const P
     return hipGetLastError();
 }
 
-hipError_t launch_pw_mid(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
+static hipError_t launch_pw_mid(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
                          const float *opart, const float *ml, int nsplit, const float *feat_in, float *feat, void *q,
                          void *k, void *v, float *vexp, hipStream_t s) {
     const int delay = g_diag_qkv_delay;  // tests only (pdsc_diag_qkv_delay): delay the split's K / V workgroups
@@ -2226,7 +1214,7 @@ hipError_t launch_pw_mid(const EncoderPlan &plan, const float *packed, const Pac
     return hipGetLastError();
 }
 
-hipError_t launch_pw_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *opart,
+static hipError_t launch_pw_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *opart,
                           const float *ml, int nsplit, const float *feat, float *feat_out, float *normed,
                           _Float16 *normed_s, float *conf, hipStream_t s) {
     const int B = plan.B, N = plan.N, Npad = plan.Npad;
@@ -2247,4 +1235,303 @@ hipError_t launch_pw_last(const EncoderPlan &plan, const float *packed, const Pa
     return hipGetLastError();
 }
 #undef PW_LAUNCH
+
+// ================================================ the row's workspace and run loop
+// measurement hook (pdsc_attention_timing): events recorded around attention launches
+static thread_local hipEvent_t *g_tstart = nullptr, *g_tstop = nullptr;
+static thread_local int g_tcap = 0;
+static thread_local int32_t *g_tcount = nullptr;
+
+EncBufs carve_encoder(Carve &c, const EncoderPlan &plan) {
+    EncBufs e;
+    const size_t B = plan.B, Npad = plan.Npad, rows = B * Npad * CH;
+    e.feat = c.take<float>(rows);
+    e.q = c.take<_Float16>(2 * rows);
+    e.k = c.take<_Float16>(2 * rows);
+    e.v = c.take<_Float16>(2 * rows);
+    e.opart = c.take<float>(rows * plan.nsplit);
+    e.ml = c.take<float>(B * Npad * plan.nsplit * 2);
+    e.vexp = c.take<float>(B * (Npad / 32));
+    e.opart1 = plan.precombine ? c.take<float>(rows) : nullptr;
+    e.ml1 = plan.precombine ? c.take<float>(B * Npad * 2) : nullptr;
+    e.q2 = e.k2 = e.v2 = nullptr;
+    e.vexp2 = nullptr;
+    // pw_mid's three Q / K / V workgroups per point tile all read the layer's
+    // residual rows while one of them writes the new PointCN rows: the rows
+    // ping-pong between feat and feat2 so no workgroup overwrites what another
+    // still reads
+    e.feat2 = plan.fused() ? nullptr : c.take<float>(rows);
+    if (plan.fused()) {
+        e.q2 = c.take<_Float16>(2 * rows);
+        e.k2 = c.take<_Float16>(2 * rows);
+        e.v2 = c.take<_Float16>(2 * rows);
+        e.vexp2 = c.take<float>(B * (Npad / 32));
+    }
+    return e;
+}
+
+// M: in the plan's layout (batch.m_layout)
+static int run_encoder(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M,
+                       const EncoderPlan &batch, const EncBufs &e, float *feat_out, float *normed, _Float16 *normed_s,
+                       float *conf, hipStream_t s, Ragged rg = {}) {
+    const EncoderPlan plan = batch.for_ragged(rg);
+    HIPCHK(launch_pw_first(plan, packed, lay, corr_pos, e.feat, e.q, e.k, e.v, e.vexp, s, rg));
+    if (plan.fused()) {  // every layer fused (0 .. L-2 with the next layer's PointCN/QKV, Q/K/V alternating between the two sets)
+        _Float16 *q = e.q, *k = e.k, *v = e.v, *q2 = e.q2, *k2 = e.k2, *v2 = e.v2;
+        float *vx = e.vexp, *vx2 = e.vexp2;
+        for (int l = 0; l + 1 < lay.L; ++l) {
+            const bool timed = g_tcap > 0 && g_tcount && *g_tcount < g_tcap;
+            if (timed) HIPCHK(hipEventRecord(g_tstart[*g_tcount], s));
+            HIPCHK(launch_attn_pw2(plan, packed, lay, l, q, k, v, vx, M, e.feat, q2, k2, v2, vx2, s, rg));
+            if (timed) HIPCHK(hipEventRecord(g_tstop[(*g_tcount)++], s));
+            std::swap(q, q2);
+            std::swap(k, k2);
+            std::swap(v, v2);
+            std::swap(vx, vx2);
+        }
+        HIPCHK(launch_attn_pw2_last(plan, packed, lay, q, k, v, vx, M, e.feat, feat_out, normed, normed_s, conf, s, rg));
+        return PDSC_OK;
+    }
+    float *feat = e.feat, *feat_alt = e.feat2;
+    for (int l = 0; l < lay.L; ++l) {
+        const bool timed = g_tcap > 0 && g_tcount && *g_tcount < g_tcap;
+        if (timed) HIPCHK(hipEventRecord(g_tstart[*g_tcount], s));
+        HIPCHK(launch_attention(plan, e.q, e.k, e.v, e.vexp, M, e.opart, e.ml, s, rg, l));
+        if (timed) HIPCHK(hipEventRecord(g_tstop[(*g_tcount)++], s));
+        const float *op = e.opart, *mlp = e.ml;
+        int ns = plan.nsplit;
+        if (plan.precombine) {
+            HIPCHK(launch_combine_rows(e.opart, e.ml, plan.B, plan.Npad, plan.nsplit, e.opart1, e.ml1, s));
+            op = e.opart1;
+            mlp = e.ml1;
+            ns = 1;
+        }
+        if (l + 1 < lay.L) {
+            HIPCHK(launch_pw_mid(plan, packed, lay, l, op, mlp, ns, feat, feat_alt, e.q, e.k, e.v, e.vexp, s));
+            std::swap(feat, feat_alt);
+        } else {
+            HIPCHK(launch_pw_last(plan, packed, lay, op, mlp, ns, feat, feat_out, normed, plan.f32 ? nullptr : normed_s,
+                                  conf, s));
+        }
+    }
+    return PDSC_OK;
+}
+
+// Ragged batches run the fused encoder as P parts of the batch (contiguous pair
+// ranges of equal pair counts), each on its own
+// stream -- the caller's and P - 1 per-device side streams, forked and joined
+// by events -- so one part's launches fill the others' dispatch tails: a ragged
+// batch's attention launches end in a tail of a few long workgroups per XCD
+// (DESIGN.md §7).  Pairs are independent through the encoder, so each part is
+// the same arithmetic on its own pointer range (bitwise equal results).
+// 128 pairs, N in [700, 1300], two halves: 4.54 -> 4.12 ms per forward (three
+// parts 4.23, four 4.32 vs two 4.19 on another box); uniform batches (two full
+// rounds of workgroups, no tail to fill) measured 3.77 -> 3.83 ms, so they stay
+// on one stream.  Knobs: PDSC_ENC_HALVES 0 never, 1 uniform batches too;
+// PDSC_ENC_PARTS P in [2, 4] (default 2).  Every part keeps the whole batch's
+// plan (the fused launches' one key split, pw2_first's layouts).
+bool enc_halves(const EncoderPlan &plan, bool ragged) {
+    const Knobs &k = knobs();
+    return plan.fused() && plan.B >= 16 * k.enc_parts && (k.enc_halves == 1 || (k.enc_halves != 0 && ragged));
+}
+// Part boundaries bounds[0 .. P]: bounds[i] = the first pair whose work prefix
+// reaches i/P of the total (counts: HOST sizes, or NULL for a uniform batch).
+void enc_bounds(const int32_t *counts, int B, int P, int *bounds) {
+    std::vector<double> pre(B + 1, 0.0);
+    for (int b = 0; b < B; ++b) pre[b + 1] = pre[b] + (counts ? (double)counts[b] * counts[b] : 1.0);
+    bounds[0] = 0;
+    bounds[P] = B;
+    for (int i = 1; i < P; ++i) {
+        const double goal = pre[B] * i / P;
+        int h = bounds[i - 1] + 1;
+        while (h < B - (P - i) && std::abs(pre[h + 1] - goal) < std::abs(pre[h] - goal)) ++h;
+        bounds[i] = h;
+    }
+}
+
+struct SideStream {
+    std::mutex mu;  // one fork / join enqueued at a time per device
+    hipStream_t s2[ENC_MAX_PARTS - 1] = {};
+    hipEvent_t fork = nullptr, join[ENC_MAX_PARTS - 1] = {};
+    bool ok = false;
+};
+// The side streams of the device that stream s runs on (the current device for
+// the legacy default stream), created there on first use.
+SideStream *side_stream(hipStream_t s) {
+    static SideStream ss[64];
+    hipDevice_t dev = 0;
+    if (!s || hipStreamGetDevice(s, &dev) != hipSuccess)
+        if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    if (dev < 0 || dev >= 64) return nullptr;
+    SideStream &x = ss[dev];
+    static std::mutex create_mu;
+    std::lock_guard<std::mutex> lock(create_mu);
+    if (!x.ok) {  // all or none (a failure leaves the forward on one stream)
+        int cur = dev;
+        if (hipGetDevice(&cur) != hipSuccess || (cur != dev && hipSetDevice(dev) != hipSuccess)) return nullptr;
+        bool ok = x.fork || hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; ok && i < ENC_MAX_PARTS - 1; ++i) {
+            if (!x.s2[i]) ok = hipStreamCreateWithFlags(&x.s2[i], hipStreamNonBlocking) == hipSuccess;
+            if (ok && !x.join[i]) ok = hipEventCreateWithFlags(&x.join[i], hipEventDisableTiming) == hipSuccess;
+        }
+        if (cur != dev) (void)hipSetDevice(cur);
+        x.ok = ok;
+    }
+    return x.ok ? &x : nullptr;
+}
+
+// The fused plan's encoder over pairs [b0, b0 + nb): every per-pair pointer
+// moved to pair b0 (the pair-major layouts of carve_encoder / carve_forward).
+static int run_encoder_part(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M,
+                            const EncoderPlan &plan, const EncBufs &e, float *normed, _Float16 *normed_s, float *conf,
+                            hipStream_t s, Ragged rg, int b0, int nb) {
+    const int N = plan.N, Npad = plan.Npad;
+    const size_t rows = (size_t)b0 * Npad * CH;
+    EncBufs eh = e;
+    eh.feat = e.feat + rows;
+    eh.q = e.q + 2 * rows;
+    eh.k = e.k + 2 * rows;
+    eh.v = e.v + 2 * rows;
+    eh.q2 = e.q2 + 2 * rows;
+    eh.k2 = e.k2 + 2 * rows;
+    eh.v2 = e.v2 + 2 * rows;
+    eh.vexp = e.vexp + (size_t)b0 * (Npad / 32);
+    eh.vexp2 = e.vexp2 + (size_t)b0 * (Npad / 32);
+    const size_t mstr = plan.m_layout == M_PACKED ? mpack_floats(N) : (size_t)N * N;
+    Ragged rh = rg;
+    if (rg.nv) rh.nv = rg.nv + b0;
+    if (rg.sv) rh.sv = rg.sv + b0;
+    if (rg.po) rh.po = rg.po + b0;
+    // (the batch's plan on nb pairs, not nb pairs' own)
+    return run_encoder(lay, packed, corr_pos + (size_t)b0 * N * lay.in_dim, M + (size_t)b0 * mstr, plan.for_pairs(nb), eh,
+                       nullptr, normed + (size_t)b0 * N * CH, normed_s + (size_t)b0 * N * 2 * CH, conf + (size_t)b0 * N, s,
+                       rh);
+}
+
+// run_encoder for the forward: the fused plan as P concurrent parts given side
+// streams ss and the part boundaries (enc_halves / enc_bounds; rg.po, when set,
+// must then order each part's pairs on its own: launch_ragged_order per part),
+// else run_encoder itself.
+int run_encoder_fwd(const PackLayout &lay, const float *packed, const float *corr_pos, const float *M,
+                    const EncoderPlan &plan, const EncBufs &e, float *normed, _Float16 *normed_s, float *conf,
+                    hipStream_t s, Ragged rg, SideStream *ss, const int *bounds, int P) {
+    if (!ss) return run_encoder(lay, packed, corr_pos, M, plan, e, nullptr, normed, normed_s, conf, s, rg);
+    std::lock_guard<std::mutex> lock(ss->mu);
+    // The side streams are shared by every caller stream of the device.  A side
+    // stream forked into another thread's graph capture stays in that capture
+    // until it ends: enqueueing there from a stream outside that capture would
+    // record into (or invalidate) the other graph, so such a call runs on one
+    // stream (bitwise the same results).
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone, c2 = hipStreamCaptureStatusNone;
+        unsigned long long id = 0, id2 = 0;
+        HIPCHK(hipStreamGetCaptureInfo(s, &cs, &id));
+        for (int i = 1; i < P; ++i) {
+            HIPCHK(hipStreamGetCaptureInfo(ss->s2[i - 1], &c2, &id2));
+            if (c2 != hipStreamCaptureStatusNone && (cs != hipStreamCaptureStatusActive || id2 != id))
+                return run_encoder(lay, packed, corr_pos, M, plan, e, nullptr, normed, normed_s, conf, s, rg);
+        }
+    }
+    HIPCHK(hipEventRecord(ss->fork, s));
+    int forked = 1, r = PDSC_OK;
+    for (; forked < P; ++forked)
+        if (hipStreamWaitEvent(ss->s2[forked - 1], ss->fork, 0) != hipSuccess) {
+            r = fail(PDSC_ERR_HIP, "hipStreamWaitEvent (fork)");
+            break;
+        }
+    for (int i = 0; r == PDSC_OK && i < P; ++i)
+        r = run_encoder_part(lay, packed, corr_pos, M, plan, e, normed, normed_s, conf, i ? ss->s2[i - 1] : s, rg,
+                             bounds[i], bounds[i + 1] - bounds[i]);
+    // join every side stream that was forked, on success AND on error: the
+    // caller's stream must not run ahead of work a side stream may still do in
+    // the workspace, and a capture must not end with an unjoined fork
+    for (int i = 1; i < forked; ++i) {
+        const hipError_t a = hipEventRecord(ss->join[i - 1], ss->s2[i - 1]);
+        const hipError_t b = a == hipSuccess ? hipStreamWaitEvent(s, ss->join[i - 1], 0) : a;
+        if (b != hipSuccess && r == PDSC_OK) r = fail(PDSC_ERR_HIP, "join: %s", hipGetErrorString(b));
+    }
+    return r;
+}
+
+// The standalone encoder's plan: on the caller's dense M (plan_encoder's dense_m_caller).
+static int encoder_plan_for(const pdsc_config *cfg, int B, int N, EncoderPlan &plan) {
+    RET_IF(check_cfg(cfg));
+    int S, k;  // (the forwards' limits hold for the standalone encoder too)
+    RET_IF(check_shape(cfg, B, N, S, k));
+    plan = plan_encoder(B, N, cfg->precision == PDSC_PRECISION_F32, true);
+    return PDSC_OK;
+}
+
 }  // namespace pdsc
+
+using namespace pdsc;
+
+extern "C" {
+
+// ---------------------------------------------------------------- a2-a4
+size_t pdsc_encoder_workspace_bytes(const pdsc_config *cfg, int32_t B, int32_t N) {
+    EncoderPlan plan;
+    if (encoder_plan_for(cfg, B, N, plan) != PDSC_OK) return 0;
+    Carve c(nullptr);
+    carve_encoder(c, plan);
+    return c.off;
+}
+
+int32_t pdsc_encoder_f32(const pdsc_config *cfg, const float *packed, const float *corr_pos,
+                         const float *M, int32_t B, int32_t N, float *feat, float *normed, float *conf,
+                         void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    EncoderPlan plan;
+    RET_IF(encoder_plan_for(cfg, B, N, plan));
+    if (!packed || !corr_pos || !M || !normed || !conf || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+    RET_IF(need_ws(ws_bytes, pdsc_encoder_workspace_bytes(cfg, B, N)));
+    Carve c(ws);
+    const EncBufs e = carve_encoder(c, plan);
+    const PackLayout lay = make_layout(cfg->num_layers, cfg->in_dim);
+    return run_encoder(lay, packed, corr_pos, M, plan, e, feat, normed, nullptr, conf, S_(stream));
+}
+
+int32_t pdsc_attention_timing(void *const *start_events, void *const *stop_events, int32_t capacity,
+                              int32_t *count) {
+    if (capacity > 0 && (!start_events || !stop_events || !count))
+        return fail(PDSC_ERR_ARG, "null events/count with capacity %d", capacity);
+    g_tstart = reinterpret_cast<hipEvent_t *>(const_cast<void **>(start_events));
+    g_tstop = reinterpret_cast<hipEvent_t *>(const_cast<void **>(stop_events));
+    g_tcap = capacity;
+    g_tcount = count;
+    return PDSC_OK;
+}
+
+int32_t pdsc_diag_qkv_delay(int32_t loops) {
+    if (loops < 0) return fail(PDSC_ERR_ARG, "loops=%d", loops);
+    g_diag_qkv_delay = loops;
+    return PDSC_OK;
+}
+
+int32_t pdsc_attention_layout(int32_t B, int32_t N, int32_t precision, int32_t *Npad, int32_t *nsplit) {
+    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
+        return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
+    if (B < 1 || N < 1 || !Npad || !nsplit) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
+    const EncoderPlan plan = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false);
+    *Npad = plan.Npad;
+    *nsplit = plan.nsplit;
+    return PDSC_OK;
+}
+
+int32_t pdsc_encoder_plan(int32_t B, int32_t N, int32_t precision, int32_t *fused) {
+    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
+        return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
+    if (B < 1 || N < 1 || !fused) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
+    const EncoderPlan plan = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false);
+    *fused = plan.fused() ? 1 : (plan.w64() ? 2 : 0);
+    return PDSC_OK;
+}
+
+int32_t pdsc_encoder_plan_vfold(int32_t B, int32_t N, int32_t precision, int32_t *vfold) {
+    if (precision != PDSC_PRECISION_H3 && precision != PDSC_PRECISION_F32)
+        return fail(PDSC_ERR_ARG, "precision %d (enum pdsc_precision)", precision);
+    if (B < 1 || N < 1 || !vfold) return fail(PDSC_ERR_ARG, "B=%d N=%d", B, N);
+    *vfold = plan_encoder(B, N, precision == PDSC_PRECISION_F32, false).vfold ? 1 : 0;
+    return PDSC_OK;
+}
+
+}  // extern "C"

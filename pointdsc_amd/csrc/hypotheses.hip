@@ -7,7 +7,7 @@
 //   post_refine  a11 <= 20 device-side IRLS refits, one workgroup per pair
 #include "abi.hpp"
 #ifdef ATT_STAMPS
-#include "attention_h3.hpp"  // the stamp buffer (BR_ST)
+#include "att_stamps.hpp"  // the stamp buffer (BR_ST)
 #endif
 #include "launch_plan.hpp"
 #include "nsm_weight.hpp"

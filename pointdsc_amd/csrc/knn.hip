@@ -5,14 +5,14 @@
 //                    row in registers): lane-minimum threshold + compaction +
 //                    (key, index) ranking; radix-select fallback
 #include "abi.hpp"
-#include "attention_h3.hpp"
+#include "h3.hpp"
 #include "launch_plan.hpp"
 
 namespace pdsc {
 
 // ------------------------------------------------------------------ a6 kNN
 // dist[b][s][j] = 2 - 2 * <normed[seed_s], normed[j]>   (models/common.py:58-60)
-// on the fp16 matrix cores with the 3-product split of attention_h3.hpp
+// on the fp16 matrix cores with the 3-product split of h3.hpp
 // (|error| <= 2^-21 on a distance in [0, 4], i.e. fp32-equivalent): ns is the
 // split copy of normed, [B][N][2][128] fp16 in qk_pos order (pw_last writes it).
 // A workgroup = 4 waves = 4 tiles of 32 seeds (lane <-> seed fragment, held in

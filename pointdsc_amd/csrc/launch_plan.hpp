@@ -1,8 +1,8 @@
 // launch_plan.hpp -- which kernels a call runs at a shape, and with which grids.
 // Host-only.  The process's knobs are read once, into Knobs.  plan_encoder
 // (encoder.hip) and plan_tail (seeds.hip), each beside the kernels' grid helpers
-// it calls, decide once per call from the call's sizes and the knobs; api.hip
-// sizes the workspace by the plans and the launchers launch what they say.
+// it calls, decide once per call from the call's sizes and the knobs; the entries
+// size the workspace by the plans and the launchers launch what they say.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -11,7 +11,7 @@
 
 namespace pdsc {
 
-constexpr int ENC_MAX_PARTS = 4;  // parts of a batch the forward's encoder may run on side streams (api.hip)
+constexpr int ENC_MAX_PARTS = 4;  // parts of a batch the forward's encoder may run on side streams (encoder.hip)
 
 // Every run-time knob of libpdsc.so (A/B measurement and bit-identity tests only;
 // the defaults are the product), read once per process, each as an integer
@@ -41,7 +41,7 @@ struct Knobs {
     bool pw_waves8;      // PDSC_PW_WAVES=4: never the 8-wave pw_mid
     bool pw_qkv_split;   // PDSC_PW_QKV_SPLIT=0: one workgroup per point tile writes Q, K and V (the same bits either way)
     bool pw_prefetch;    // PDSC_PW_PREFETCH=0: the Q / K / V split chain without the panel prefetch (message_resid + pcn_qkv8)
-    // ---- the forward's encoder parts and ragged order (api.hip)
+    // ---- the encoder parts (encoder.hip) and the ragged order (api.hip) of the forward
     int enc_halves;  // PDSC_ENC_HALVES: 0 never, 1 uniform batches too, else ragged batches only
     int enc_parts;   // PDSC_ENC_PARTS=P in [2, ENC_MAX_PARTS] (default 2)
     // PDSC_ENC_BAL=1: parts of equal work sum(n^2) instead of equal pair counts

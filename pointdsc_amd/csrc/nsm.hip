@@ -6,7 +6,8 @@
 //   nsm_finish   a8  pair- or batch-global early exit t* = first iterate where every seed
 //                    is allclose (torch.allclose over the whole batch, :354)
 #include "abi.hpp"
-#include "attention_h3.hpp"
+#include "att_stamps.hpp"
+#include "h3.hpp"
 #include "launch_plan.hpp"
 #include "nsm_weight.hpp"
 
@@ -78,7 +79,7 @@ PDSC_DEV unsigned power_iterate(const float *trow_lds, int tstride, int k, int T
 
 // nsm_seed_kernel: one WAVE per (seed, pair), 4 seeds per workgroup.  The
 // k x k feature Gram matrix of the seed's neighbourhood comes from the fp16
-// matrix cores with the 3-product split (attention_h3.hpp), its operands read
+// matrix cores with the 3-product split (h3.hpp), its operands read
 // straight from the split normed copy ns [B][N][2][128] (the same bytes the
 // seed kNN reads) into registers: tiles (0,0), (0,1), (1,1) of 32 x 32 for
 // k <= 64.  T = F o S (diag 0, :257-278) goes to the wave's slice of LDS, each

@@ -151,7 +151,6 @@ inline PackLayout make_layout(int L, int in_dim) {
 // Every pair's buffers keep the batch stride N (the largest pair); pair b uses
 // its first nv[b] rows and has sv[b] = int(nv[b] * ratio) seeds (S = the
 // largest).  nv == sv == nullptr: a uniform batch (every pair N rows, S seeds).
-extern thread_local int g_diag_qkv_delay;  // api.hip: pdsc_diag_qkv_delay (tests only)
 struct Ragged {
     const int *nv = nullptr, *sv = nullptr;
     // the attention's pair order (longest pairs first, dealt over the XCDs), or null
@@ -180,17 +179,6 @@ hipError_t launch_compat(const float *src, const float *tgt, int B, int N, const
 hipError_t launch_compat_packed(const float *src, const float *tgt, int B, int N, const float *sigma_d,
                                 float *Mp, hipStream_t s, Ragged rg = {});
 
-hipError_t launch_pack_dense(const float *w, const float *b, const float *bn_w, const float *bn_b,
-                             const float *bn_rm, const float *bn_rv, int in, int out, bool f32, float *dst_w,
-                             float *dst_b, float *dst_a, float *dst_beta, float *dst_scale, hipStream_t s);
-hipError_t launch_copy(const float *src, float *dst, int n, hipStream_t s);
-// The V fold's weights in fp64, each rounded once to fp32: wm [CH2][CH] = W0 Wv, bm [CH2] = W0 bv + b0.
-hipError_t launch_fold_vm(const float *w0, const float *b0, const float *wv, const float *bv, float *wm, float *bm,
-                          hipStream_t s);
-
-// Attention partials for one layer: opart [B][nsplit][Npad x CH], ml [B][nsplit][Npad][2];
-// opart rows [Npad][CH] for f32, the fragment-block tiling of attention_h3.hpp
-// (h3_opart_off) for H3.
 // M's layouts: dense [B][N][N], symmetric-packed (mpack_*)
 enum MLayout { M_DENSE = 0, M_PACKED = 1 };
 // The encoder's and the tail's launchers launch what the call's plans say
@@ -198,56 +186,6 @@ enum MLayout { M_DENSE = 0, M_PACKED = 1 };
 // plan_tail).
 struct EncoderPlan;
 struct TailPlan;
-// q, k, v: the fp16 hi/lo split layouts of attention_h3.hpp (4 B per element),
-// or fp32 [B][Npad][CH] rows for the exact-fp32 plan (attention.hpp).
-// M: dense [B][N][N] or symmetric-packed [B][mpack_floats(N)], per plan.m_layout.
-// vexp: [B][Npad/32] V-tile exponents of the H3 layout (attention_h3.hpp); unused for f32.
-hipError_t launch_attention(const EncoderPlan &plan, const void *q, const void *k, const void *v, const float *vexp,
-                            const float *M, float *opart, float *ml, hipStream_t s, Ragged rg = {}, int layer = 0);
-// The fused plan: attention of layer `layer` on (q, k, v, vexp_in) + the pointwise
-// chain to the layer-(layer+1) (qo, ko, vo, vexp_out), H3 layouts; feat updated in
-// place (encoder.hip: attn_pw2_kernel).
-hipError_t launch_attn_pw2(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
-                           const void *q, const void *k, const void *v, const float *vexp_in, const float *M,
-                           float *feat, void *qo, void *ko, void *vo, float *vexp_out, hipStream_t s, Ragged rg = {});
-// The fused plan: attention of the last layer on (q, k, v, vexp_in) + its fc_message, residual,
-// F.normalize and classifier (encoder.hip: attn_pw2_last_kernel); outputs as launch_pw_last.
-hipError_t launch_attn_pw2_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const void *q,
-                                const void *k, const void *v, const float *vexp_in, const float *M, const float *feat,
-                                float *feat_out, float *normed, _Float16 *normed_s, float *conf, hipStream_t s,
-                                Ragged rg = {});
-// fp32 rows [B][N][CH] -> [B][Npad][CH], padding rows zero.
-hipError_t launch_pad_rows(const float *x, int B, int N, int Npad, float *y, hipStream_t s);
-// fp32 q, k, v [B][ld][CH] -> split layouts (rows N..Npad-1 zero).
-hipError_t launch_split_qkv(const float *q, const float *k, const float *v, int B, int N, int ld, int Npad,
-                            _Float16 *qs, _Float16 *ks, _Float16 *vs, float *vexp, hipStream_t s);
-// Combine partials -> msg [B][Npad][CH] (used by the standalone attention API).
-hipError_t launch_attn_combine(const float *opart, const float *ml, bool f32, int B, int N, int Npad,
-                               int nsplit, float *msg, hipStream_t s);
-
-// Pointwise chains (one workgroup per PT points) in the plan's form, over the
-// plan's B pairs; q, k, v in launch_attention's layouts.
-// plan.vfold (the register-chained kernels only): V is the folded
-// 64-channel V' in the first half of every V tile (the second half zero unless
-// fused, for attention_w64's 128-channel P.V), the partials' first 64 channels
-// are the folded O, and the message chain starts at fc0's BatchNorm / ReLU.
-hipError_t launch_pw_first(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *corr_pos,
-                           float *feat, void *q, void *k, void *v, float *vexp, hipStream_t s, Ragged rg = {});
-// H3 split partials (nsplit) -> one combined split (opart1 [B][Npad][CH] in the
-// h3 tiling, ml1 = (0, 1)) that pw_mid / pw_last read with nsplit = 1 (small
-// batches: combine16's per-thread load chain is the pointwise launch's latency).
-hipError_t launch_combine_rows(const float *opart, const float *ml, int B, int Npad, int nsplit, float *opart1,
-                               float *ml1, hipStream_t s);
-// feat_in: the layer's rows (the residual); feat: where the new PointCN rows
-// go -- a different buffer (the Q / K / V workgroups of one point tile read
-// feat_in while one of them writes feat)
-hipError_t launch_pw_mid(const EncoderPlan &plan, const float *packed, const PackLayout &lay, int layer,
-                         const float *opart, const float *ml, int nsplit, const float *feat_in, float *feat, void *q,
-                         void *k, void *v, float *vexp, hipStream_t s);
-hipError_t launch_pw_last(const EncoderPlan &plan, const float *packed, const PackLayout &lay, const float *opart,
-                          const float *ml, int nsplit, const float *feat, float *feat_out, float *normed,
-                          _Float16 *normed_s, float *conf, hipStream_t s);
-
 // The tail: tp = plan_tail(B, N, S) of the call's own B, N and S.
 hipError_t launch_local_max(const TailPlan &tp, const float *src, const float *conf, int B, int N, float radius,
                             float *lm, hipStream_t s, Ragged rg = {});

@@ -9,7 +9,7 @@
 //              fp64 partial sums: one workgroup per (pair, 64-row strip), then a
 //              fixed-order per-pair reduction
 #include "abi.hpp"
-#include "attention_h3.hpp"
+#include "h3.hpp"
 
 namespace pdsc {
 

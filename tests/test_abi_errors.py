@@ -1,5 +1,6 @@
-"""The argument checks of every f-row entry point and of the a-row stage entries
-that take only pointers and scalars, replayed against a recorded
+"""The argument checks of every f-row entry point, of the a-row stage entries
+that take only pointers and scalars, and of the encoder row's weight, encoder,
+attention, timing, layout and plan entries, replayed against a recorded
 table (tests/golden/abi_errors/abi_errors.json) -- no GPU needed: every call
 here is rejected on the host before the entry's first HIP call.
 
@@ -31,6 +32,21 @@ BIG = 1 << 40    # a workspace size that passes every need_ws
 def short(query, *args):
     """ws_bytes one byte short of `query(*args)`."""
     return {"short_of": [query, list(args)]}
+
+
+def cfg(**fields):
+    """A pdsc_config argument: _lib.make_config()'s defaults (3 layers) with `fields` set."""
+    return {"cfg": fields}
+
+
+def ptrs(n, null_at):
+    """An array of n dummy pointers with entry `null_at` NULL (pdsc_pack_weights' parameter list)."""
+    return {"ptrs": [n, null_at]}
+
+
+C0 = cfg()
+ENC_WS = ("pdsc_encoder_workspace_bytes", C0, 2, 100)
+ATT_WS = ("pdsc_attention_workspace_bytes", 2, 100, 128, 0)
 
 
 # entry -> (a VALID argument list, [overrides breaking one check each], [overrides breaking two checks])
@@ -210,6 +226,58 @@ ENTRIES = {
         [P, P, P, 2, 100, 0.1, None],
         [{0: None}, {1: None}, {2: None}, {3: 0}, {4: 0}],
         [{1: None, 3: 0}, {0: None, 4: 0}]),
+    # a2-a4: the weights (pack.hip); check_cfg's branches are reached here
+    "pdsc_pack_weights": (
+        [C0, P, P, None],
+        [{0: None}, {0: cfg(num_channels=64)}, {0: cfg(num_layers=0)}, {0: cfg(num_layers=65)}, {0: cfg(in_dim=0)},
+         {0: cfg(in_dim=129)}, {0: cfg(num_iterations=-1)}, {0: cfg(num_iterations=32)}, {0: cfg(k=0)},
+         {0: cfg(precision=2)}, {1: None}, {2: None}, {1: ptrs(88, 0)}, {1: ptrs(88, 30)}, {1: ptrs(88, 87)}],
+        [{0: None, 1: None}, {0: cfg(num_channels=64, num_layers=0)}, {0: cfg(num_layers=0, in_dim=0)},
+         {0: cfg(in_dim=0, num_iterations=32)}, {0: cfg(num_iterations=32, k=0)}, {0: cfg(k=0, precision=2)},
+         {0: cfg(precision=2), 1: None}, {2: None, 1: ptrs(88, 5)}]),
+    "pdsc_packed_block": (
+        [C0, 0, 0, P],
+        [{0: None}, {0: cfg(in_dim=129)}, {1: -1}, {1: 3}, {2: -1}, {2: 8}, {3: None}],
+        [{0: cfg(num_layers=65), 1: -1}, {1: 3, 2: 8}, {2: 8, 3: None}]),
+    # a2-a4: the standalone encoder (encoder.hip); the shape checks are reached here
+    "pdsc_encoder_f32": (
+        [C0, P, P, P, 2, 100, None, P, P, P, BIG, None],
+        [{0: None}, {0: cfg(precision=2)}, {4: 0}, {5: 1}, {5: 32768}, {5: 5}, {0: cfg(k=64)}, {0: cfg(ratio=0.001)},
+         {1: None}, {2: None}, {3: None}, {7: None}, {8: None}, {9: None}, {10: short(*ENC_WS)}],
+        [{0: cfg(k=0), 4: 0}, {4: 0, 5: 32768}, {5: 32768, 0: cfg(ratio=0.00001)}, {5: 5, 0: cfg(k=64)},
+         {0: cfg(k=64), 1: None}, {5: 1, 1: None}, {3: None, 10: short(*ENC_WS)}]),
+    # a3: the standalone attention (attention.hip)
+    "pdsc_attention_f32": (
+        [P, P, P, P, 2, 100, 128, 0, P, P, BIG, None],
+        [{6: 64}, {0: None}, {1: None}, {2: None}, {3: None}, {8: None}, {9: None}, {4: 0}, {5: 0}, {5: 32768}, {7: 2},
+         {7: -1}, {10: short(*ATT_WS)}],
+        [{6: 64, 0: None}, {8: None, 4: 0}, {5: 32768, 7: 2}, {0: None, 7: 2}, {4: 0, 10: short(*ATT_WS)}]),
+    # the row's timing, layout and plan queries (encoder.hip) and the forward's plan query (api.hip)
+    "pdsc_attention_timing": (
+        [P, P, 4, P],
+        [{0: None}, {1: None}, {3: None}],
+        [{0: None, 3: None}]),
+    "pdsc_diag_qkv_delay": (
+        [0],
+        [{0: -1}],
+        []),
+    "pdsc_attention_layout": (
+        [2, 100, 0, P, P],
+        [{2: 2}, {2: -1}, {0: 0}, {1: 0}, {3: None}, {4: None}],
+        [{2: 2, 0: 0}, {1: 0, 3: None}]),
+    "pdsc_encoder_plan": (
+        [2, 100, 0, P],
+        [{2: 2}, {0: 0}, {1: 0}, {3: None}],
+        [{2: 2, 3: None}, {0: 0, 1: 0}]),
+    "pdsc_encoder_plan_vfold": (
+        [2, 100, 0, P],
+        [{2: 2}, {0: 0}, {1: 0}, {3: None}],
+        [{2: 2, 3: None}, {0: 0, 1: 0}]),
+    "pdsc_launch_plan": (
+        [C0, 2, 100, P, 13],
+        [{0: None}, {0: cfg(num_layers=0)}, {1: 0}, {2: 1}, {2: 32768}, {2: 5}, {0: cfg(k=64)}, {3: None}, {3: None, 4: 12}],
+        [{0: cfg(in_dim=0), 1: 0}, {2: 32768, 0: cfg(ratio=0.00001)}, {2: 5, 0: cfg(k=64)}, {0: cfg(k=64), 3: None},
+         {1: 0, 4: 12}]),
 }
 
 
@@ -219,7 +287,7 @@ def cases():
     for entry, (valid, singles, pairs) in ENTRIES.items():
         for kind, overrides in (("check", singles), ("precedence", pairs)):
             for o in overrides:
-                assert kind == "check" or len(o) == 2 or entry == "pdsc_ply_read_xyz", (entry, o)
+                assert kind == "check" or len(o) in (1, 2) or entry == "pdsc_ply_read_xyz", (entry, o)
                 args = list(valid)
                 for i, v in o.items():
                     args[i] = v
@@ -243,10 +311,21 @@ def bind(path=None):
 _DUMMY = ctypes.create_string_buffer(256)
 
 
-def _convert(lib, v, ctype):
+def _convert(lib, v, ctype, protos=None):
+    if isinstance(v, dict) and "cfg" in v:
+        from pointdsc_amd import _lib
+        c = _lib.make_config(num_layers=3)
+        for k, x in v["cfg"].items():
+            setattr(c, k, x)
+        return ctypes.pointer(c)
+    if isinstance(v, dict) and "ptrs" in v:
+        n, null_at = v["ptrs"]
+        arr = (ctypes.c_void_p * n)(*([ctypes.addressof(_DUMMY)] * n))
+        arr[null_at] = None
+        return arr
     if isinstance(v, dict):
         query, qargs = v["short_of"]
-        size = getattr(lib, query)(*qargs)
+        size = getattr(lib, query)(*(_convert(lib, a, t) for a, t in zip(qargs, protos[query][1])))
         assert size > 0, (query, qargs)
         return size - 1
     if v == P:
@@ -270,11 +349,11 @@ def replay(lib, protos):
     for entry, _, args in cases():
         argtypes = protos[entry][1]
         assert len(args) == len(argtypes), entry
-        call = [_convert(lib, v, t) for v, t in zip(args, argtypes)]
+        call = [_convert(lib, v, t, protos) for v, t in zip(args, argtypes)]
         status = getattr(lib, entry)(*call)
         msg = lib.pdsc_last_error().decode()
         for v, c in zip(args, call):
-            if isinstance(v, dict):
+            if isinstance(v, dict) and "short_of" in v:
                 msg = msg.replace(f"{c} < {c + 1} bytes", "<size-1> < <size> bytes")
         got.append((int(status), msg))
     return got
@@ -310,11 +389,11 @@ def test_table_covers_every_moved_entry():
     for entry, (valid, singles, pairs) in ENTRIES.items():
         assert len(valid) == len(protos[entry][1]), entry
         assert singles, entry
-        if entry != "pdsc_ply_read_xyz":
+        if entry not in ("pdsc_ply_read_xyz", "pdsc_diag_qkv_delay"):
             assert pairs, entry
         if ctypes.c_size_t in protos[entry][1]:
-            assert any(isinstance(v, dict) for o in singles for v in o.values()), entry
-            assert any(isinstance(v, dict) for o in pairs for v in o.values()), entry
+            assert any(isinstance(v, dict) and "short_of" in v for o in singles for v in o.values()), entry
+            assert any(isinstance(v, dict) and "short_of" in v for o in pairs for v in o.values()), entry
 
 
 if __name__ == "__main__":

@@ -145,7 +145,7 @@ def test_ragged_uniform_equals_batched(gpu_device):
 @pytest.mark.parametrize("B", [64, 65, 128])
 def test_ragged_halves_equal_uniform(B, gpu_device):
     """From 32 pairs on the fused plan a ragged batch runs the encoder as two half
-    batches on two streams (api.hip: run_encoder_fwd), each keeping the whole
+    batches on two streams (encoder.hip: run_encoder_fwd), each keeping the whole
     batch's plan (at 64 pairs a half of 32 alone would take the unfused chains);
     with every count N it is bitwise the uniform forward, which stays on one
     stream.  (Odd splits: test_ragged_vs_single_forwards[130] and the other

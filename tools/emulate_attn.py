@@ -33,7 +33,7 @@ def mm3(a, b):  # a [n,k] @ b [k,m] from hi / lo pairs, fp32 accumulation (lo.lo
 
 
 def vexp(vmax, target=14):
-    """attention_h3.hpp h3_vexp: the largest e <= VEXP_MAX with vmax 2^e < 2^target"""
+    """h3.hpp h3_vexp: the largest e <= VEXP_MAX with vmax 2^e < 2^target"""
     if not (vmax > 0) or not (vmax < 8192):
         return 0
     _, ex = np.frexp(np.float32(vmax))

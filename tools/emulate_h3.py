@@ -1,4 +1,4 @@
-"""Numerics check of the 3xf16 product split (attention_h3.hpp) on the CPU.
+"""Numerics check of the 3xf16 product split (h3.hpp) on the CPU.
 
 Runs the oracle's encoder (oracle/pdsc_oracle.py) on the golden cases with
 Q K^T and/or P V replaced by an emulation of the kernel's arithmetic --

@@ -1,4 +1,4 @@
-// tools/split_probe.hip -- checks split2 (attention_h3.hpp: v_cvt_pk_f16_f32 + v_fma_mixlo/mixhi)
+// tools/split_probe.hip -- checks split2 (h3.hpp: v_cvt_pk_f16_f32 + v_fma_mixlo/mixhi)
 // against the reference split hi = f16(x), lo = f16(x - hi) on 131072 values incl.
 // fp16 ties, subnormal and large magnitudes (diagnostics; run on the GPU box).
 // Build: hipcc --offload-arch=gfx950 -O3 tools/split_probe.hip -o /tmp/split_probe
