@@ -1127,6 +1127,95 @@ int32_t pdsc_pose_graph_linearize(const double *poses, int32_t n, const int32_t 
                                   double *residual, double *objective, double *H, double *b, void *workspace,
                                   size_t workspace_bytes, pdsc_stream_t stream);
 
+/* ------------------------------------------- f8 FCGF descriptors ----------
+ * misc/fcgf.py's ResUNetBN2C(in_channels 1, out_channels C_out, conv1_kernel_size
+ * 5 | 7, normalize_feature) in eval mode -- the sparse 3-D ResUNet that
+ * demo_registration.py:11-35, misc/cal_fcgf.py:12-85 and datasets/
+ * LidarFeatureExtractor.py:166-200 run through MinkowskiEngine -- on the GPU.
+ * MinkowskiEngine and the released FCGF checkpoints are not available to this
+ * build: the semantics below are a restatement, and parity with MinkowskiEngine
+ * itself and with the released checkpoints is UNPINNED.  The choices, fixed here:
+ *
+ *   quantise   coords = floor(xyz / voxel_size) in fp32 (an IEEE divide, not a
+ *              reciprocal multiply; misc/cal_fcgf.py:73); one point per occupied
+ *              voxel, the one with the lowest input index; voxels in ascending
+ *              (batch, x, y, z) key order (pdsc_voxel_down_sample's convention);
+ *              callers take xyz[inds], the kept ORIGINAL points, and the input
+ *              feature 1 as [m,1].  Coordinates may be negative; each must lie in
+ *              [-2^18, 2^18) and the batch index in [0, 64) (a 63-bit key), else
+ *              PDSC_ERR_UNSUPPORTED.
+ *   levels     tensor strides 1, 2, 4, 8.  A stride-2 convolution at tensor stride
+ *              t has the outputs unique(floor(c / 2t) 2t) (floor: negatives round
+ *              down).  A transposed convolution creates no coordinates: its outputs
+ *              are the encoder's set at that stride, so ME.cat is row-aligned.
+ *   kernel map HYPER_CUBE, centred: offsets o in {-r..r}^3 t_in, r = 1, 2, 3 for
+ *              kernel sizes 3, 5, 7; output u reads input u + o; the weight index
+ *              is k = (o_x + r) + K (o_y + r) + K^2 (o_z + r) (fcgf_kernel_index,
+ *              csrc/fcgf.hip).  A checkpoint's kernel axis is read through
+ *              fcgf_checkpoint_index (the same order today): if MinkowskiEngine's
+ *              offset order differs, that ONE function changes.  A transposed
+ *              convolution's map is the stride-2 convolution's with input and
+ *              output swapped and the same k (<= 8 coarse parents per voxel).
+ *   network    ResUNet2.forward (misc/fcgf.py:800-851), CHANNELS 32/64/128/256,
+ *              TR_CHANNELS 64/64/64/128; BasicBlockBN (:142-158);
+ *              MinkowskiBatchNorm in eval mode = BatchNorm1d(eps 1e-5) on the rows,
+ *              folded into a scale and a shift; concatenation (upsampled, skip);
+ *              output F / (||F||_2 + 1e-8) when normalize != 0.  fp32 throughout
+ *              (exact fp32 MFMA), fixed summation order, no scatter: results are
+ *              bitwise reproducible and independent of the rest of the batch.
+ *
+ * Parameters: ONE flat fp32 device buffer of pdsc_fcgf_param_floats floats in
+ * state-dict order without num_batches_tracked: conv1.kernel [K^3,1,32],
+ * norm1.bn.{weight, bias, running_mean, running_var}, block1.conv1.kernel
+ * [27,32,32], block1.norm1.bn.*, block1.conv2.kernel, block1.norm2.bn.*,
+ * conv2.kernel, norm2.bn.*, block2.*, conv3, norm3, block3, conv4, norm4, block4,
+ * conv4_tr, norm4_tr, block4_tr, conv3_tr, norm3_tr, block3_tr, conv2_tr,
+ * norm2_tr, block2_tr, conv1_tr.kernel [96,64], final.kernel [64,C_out],
+ * final.bias [C_out]; every kernel [K^3, C_in, C_out] row-major.
+ * pdsc_fcgf_pack_weights writes the folded device layout (csrc/fcgf.hip:
+ * pack_layer_kernel) of pdsc_fcgf_packed_floats floats.  1 <= C_out <= 32.      */
+size_t pdsc_fcgf_param_floats(int32_t conv1_kernel_size, int32_t out_channels);
+size_t pdsc_fcgf_packed_floats(int32_t conv1_kernel_size, int32_t out_channels);
+int32_t pdsc_fcgf_pack_weights(const float *params, int32_t conv1_kernel_size, int32_t out_channels, float *packed,
+                               pdsc_stream_t stream);
+/* The workspace of pdsc_fcgf_quantize (n_points points) and pdsc_fcgf_forward
+ * (m = n_points voxels): a pure function of its arguments that bounds the worst
+ * case of every level holding n_points voxels; 0 for unsupported arguments.     */
+size_t pdsc_fcgf_workspace_bytes(int32_t n_points, int32_t batch, int32_t conv1_kernel_size, int32_t out_channels);
+/* xyz [n,3]; batch_offsets: device int32 [batch + 1], cloud b = points
+ * offsets[b] .. offsets[b + 1] - 1 (NULL with batch == 1); inds [n] capacity
+ * (input index of each kept point), coords [n,4] capacity (batch, x, y, z), both
+ * in ascending key order; *count (device int32) = voxels.  Synchronises `stream`
+ * (reports the range error found on the device).                              */
+int32_t pdsc_fcgf_quantize(const float *xyz, int32_t n, const int32_t *batch_offsets, int32_t batch, float voxel_size,
+                           int32_t *inds, int32_t *coords, int32_t *count, void *workspace, size_t workspace_bytes,
+                           pdsc_stream_t stream);
+/* Optional intermediates of pdsc_fcgf_forward (any member may be NULL): the
+ * feature tensors after block1..4, block4_tr..2_tr and conv1_tr (+ ReLU), each
+ * [m, C] capacity with the level's first counts[level] rows valid -- level-1
+ * tensors in the caller's row order, coarser ones in ascending key order --,
+ * the coordinates [m,4] of the levels of tensor stride 2, 4, 8 and counts [4].  */
+typedef struct pdsc_fcgf_debug {
+    float *block1;      /* [m,32]   stride 1 */
+    float *block2;      /* [m,64]   stride 2 */
+    float *block3;      /* [m,128]  stride 4 */
+    float *block4;      /* [m,256]  stride 8 */
+    float *block4_tr;   /* [m,128]  stride 4 */
+    float *block3_tr;   /* [m,64]   stride 2 */
+    float *block2_tr;   /* [m,64]   stride 1 */
+    float *conv1_tr;    /* [m,64]   stride 1 */
+    int32_t *coords2;   /* [m,4] */
+    int32_t *coords4;   /* [m,4] */
+    int32_t *coords8;   /* [m,4] */
+    int32_t *counts;    /* [4] voxels per level */
+} pdsc_fcgf_debug;
+/* coords [m,4] int32 (batch, x, y, z), unique rows in any order (pdsc_fcgf_quantize's
+ * output); feats [m,1] (NULL: the constant 1); out [m, out_channels], row i the
+ * descriptor of coords row i.  Synchronises `stream` (range errors).          */
+int32_t pdsc_fcgf_forward(const float *packed, int32_t conv1_kernel_size, int32_t out_channels, int32_t normalize,
+                          const int32_t *coords, const float *feats, int32_t m, float *out,
+                          const pdsc_fcgf_debug *debug, void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+
 /* ----------------------------------------------- full testing forward ------
  * PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197)
  * for B independent pairs: compat -> encoder -> classifier -> seeds -> kNN ->

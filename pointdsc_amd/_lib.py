@@ -135,6 +135,12 @@ class PdscPoseGraphResult(ctypes.Structure):
                 ("edges_kept", c_int32), ("solver_failed", c_int32)]
 
 
+class PdscFcgfDebug(ctypes.Structure):
+    """``struct pdsc_fcgf_debug`` (include/pdsc.h): optional taps of pdsc_fcgf_forward."""
+    _fields_ = [("block1", vp), ("block2", vp), ("block3", vp), ("block4", vp), ("block4_tr", vp), ("block3_tr", vp),
+                ("block2_tr", vp), ("conv1_tr", vp), ("coords2", vp), ("coords4", vp), ("coords8", vp), ("counts", vp)]
+
+
 # enum pdsc_edge_mode (include/pdsc.h)
 EDGE_MODES = {"squared": 0, "length": 1}
 
@@ -244,6 +250,13 @@ _PROTOS = {
                                            vp]),
     "pdsc_pose_graph_linearize": (c_int32, [vp, c_int32, vp, vp, vp, vp, vp, c_int32, vp, c_double, c_int32, vp, vp,
                                             vp, vp, vp, c_size_t, vp]),
+    "pdsc_fcgf_param_floats": (c_size_t, [c_int32, c_int32]),
+    "pdsc_fcgf_packed_floats": (c_size_t, [c_int32, c_int32]),
+    "pdsc_fcgf_pack_weights": (c_int32, [vp, c_int32, c_int32, vp, vp]),
+    "pdsc_fcgf_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "pdsc_fcgf_quantize": (c_int32, [vp, c_int32, vp, c_int32, c_float, vp, vp, vp, vp, c_size_t, vp]),
+    "pdsc_fcgf_forward": (c_int32, [vp, c_int32, c_int32, c_int32, vp, vp, c_int32, vp, ctypes.POINTER(PdscFcgfDebug),
+                                    vp, c_size_t, vp]),
     "pdsc_forward_training_workspace_bytes": (c_size_t, [CFG, c_int32, c_int32]),
     "pdsc_range_status": (c_int32, [vp, c_int32, ctypes.POINTER(c_int32), vp]),
     "pdsc_range_poll": (c_int32, [vp, c_int32, vp]),

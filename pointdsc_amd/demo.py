@@ -1,14 +1,17 @@
 """demo_registration.py of AmnonDrory/PointDSC on the MI355X path (configs[0]):
-two PLY clouds -> FPFH on the GPU (pointdsc_amd.descriptors) -> nearest-
-neighbour matching (pointdsc_amd.correspondence, use_mutual=False as the demo's
+two PLY clouds -> FPFH (pointdsc_amd.descriptors) or FCGF (pointdsc_amd.fcgf)
+descriptors on the GPU -> nearest-neighbour matching (pointdsc_amd.correspondence, use_mutual=False as the demo's
 argmin, :101-108) -> PointDSC testing forward (:111-117).
 
     python -m pointdsc_amd.demo --pcd1 cloud_bin_0.ply --pcd2 cloud_bin_1.ply \\
         [--weights model_best.pkl] [--config config.json] [--out result.npz]
+        [--descriptor fcgf --fcgf_weights ResUNetBN2C-feat32-3dmatch-v0.05.pth]
 
 Differences from the reference driver, all deliberate:
-  * --descriptor fcgf is refused: FCGF needs MinkowskiEngine and its release
-    checkpoint (misc/fcgf.py), outside this build's scope.
+  * --descriptor fcgf needs --fcgf_weights FILE (a checkpoint with a
+    'state_dict' entry in MinkowskiEngine's names, demo_registration.py:16-33):
+    no FCGF checkpoint is distributed here, and parity of the GPU restatement
+    with MinkowskiEngine and the released checkpoints is unpinned (fcgf.py).
   * --use_gpu False is refused: this build has no CPU execution path (the
     product never falls back to the CPU or to the test oracle); the reference
     runs the same model on the CPU there.
@@ -48,15 +51,37 @@ def build_model(config: dict, weights: str | None, device):
     return model.to(device).eval()
 
 
-def register(model, pcd1, pcd2, downsample: float, device, orient: str = "open3d"):
+def build_fcgf(weights: str, device):
+    """The demo's FCGF model (demo_registration.py:16-24): ResUNetBN2C(1, 32,
+    bn_momentum=0.05, conv1_kernel_size=7, normalize_feature=True) with the
+    checkpoint's 'state_dict'."""
+    from .fcgf import FCGF
+    model = FCGF(1, 32, bn_momentum=0.05, conv1_kernel_size=7, normalize_feature=True)
+    model.load_state_dict(torch.load(weights, map_location="cpu", weights_only=True)["state_dict"], strict=True)
+    return model.to(device).eval()
+
+
+def register(model, pcd1, pcd2, downsample: float, device, orient: str = "open3d", descriptor: str = "fpfh",
+             fcgf_model=None):
     """The demo's pipeline for two clouds (paths or [n,3] arrays): returns a dict
     with final_trans [4,4], final_labels [n], the correspondence inputs and the
     downsampled points / features of both clouds.  orient: the normals' sign
-    (descriptors.estimate_normals; 'open3d' = the reference's)."""
+    (descriptors.estimate_normals; 'open3d' = the reference's).  descriptor
+    'fcgf': quantise -> FCGF (fcgf_model, build_fcgf) instead of FPFH
+    (demo_registration.py:11-35)."""
     from . import descriptors as D
     from .correspondence import build_correspondences
+    if descriptor not in ("fpfh", "fcgf"):
+        raise ValueError(f"descriptor must be 'fpfh' or 'fcgf', got {descriptor!r}")
+    if descriptor == "fcgf" and fcgf_model is None:
+        raise ValueError("descriptor 'fcgf' needs fcgf_model (demo.build_fcgf)")
 
     def feats(pcd):
+        if descriptor == "fcgf":
+            from .fcgf import extract_features
+            raw = torch.as_tensor(D.read_ply(pcd) if isinstance(pcd, str) else np.asarray(pcd, np.float32)).to(device)
+            pts, f = extract_features(fcgf_model, raw, downsample)
+            return raw, pts, f
         if isinstance(pcd, str):
             return D.extract_fpfh_features(pcd, downsample, device, orient)
         raw = torch.as_tensor(np.asarray(pcd, np.float32)).to(device)
@@ -80,6 +105,9 @@ def main(argv=None):
     ap.add_argument("--pcd1", default="demo_data/cloud_bin_0.ply")
     ap.add_argument("--pcd2", default="demo_data/cloud_bin_1.ply")
     ap.add_argument("--descriptor", default="fpfh", choices=["fcgf", "fpfh"])
+    ap.add_argument("--fcgf_weights", default=None,
+                    help="FCGF checkpoint with a 'state_dict' entry (torch.load weights_only=True); needed by "
+                         "--descriptor fcgf")
     ap.add_argument("--use_gpu", default="True")
     ap.add_argument("--config", default=None, help="a snapshot config.json (default: the 3DMatch release values)")
     ap.add_argument("--weights", default=None, help="state dict (torch.load weights_only=True)")
@@ -87,8 +115,9 @@ def main(argv=None):
     ap.add_argument("--normals", default="open3d", choices=["open3d", "centroid"],
                     help="normal sign: open3d 0.9's (the reference's) or towards the cloud's centroid")
     a = ap.parse_args(argv)
-    if a.descriptor != "fpfh":
-        sys.exit("descriptor 'fcgf' needs MinkowskiEngine and the FCGF checkpoint: out of scope (use --descriptor fpfh)")
+    if a.descriptor == "fcgf" and not a.fcgf_weights:
+        sys.exit("--descriptor fcgf needs --fcgf_weights FILE (an FCGF checkpoint with a 'state_dict' entry; none is "
+                 "distributed with this build)")
     if a.use_gpu.lower() in ("false", "0", "no", "n", "f"):
         sys.exit("--use_gpu False: this build has no CPU execution path (see DESIGN.md)")
     config = dict(RELEASE_3DMATCH)
@@ -97,7 +126,8 @@ def main(argv=None):
             config.update({k: v for k, v in json.load(f).items() if k in RELEASE_3DMATCH})
     device = torch.device("cuda")
     model = build_model(config, a.weights, device)
-    res = register(model, a.pcd1, a.pcd2, config["downsample"], device, a.normals)
+    fcgf_model = build_fcgf(a.fcgf_weights, device) if a.descriptor == "fcgf" else None
+    res = register(model, a.pcd1, a.pcd2, config["downsample"], device, a.normals, a.descriptor, fcgf_model)
     T = res["final_trans"].cpu().numpy()
     print(f"{len(res['corr'])} correspondences, {int((res['final_labels'] > 0).sum())} inliers")
     print("final_trans =\n" + np.array2string(T, precision=6, suppress_small=True))
