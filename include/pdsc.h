@@ -1127,6 +1127,180 @@ int32_t pdsc_pose_graph_linearize(const double *poses, int32_t n, const int32_t 
                                   double *residual, double *objective, double *H, double *b, void *workspace,
                                   size_t workspace_bytes, pdsc_stream_t stream);
 
+/* ------------------------------ f13 RGB-D odometry, hybrid term (fragments) --
+ * open3d 0.10's compute_rgbd_odometry with RGBDOdometryJacobianFromHybridTerm, as
+ * multiway/make_fragments.py:41-61 calls it on adjacent frames, batched over P
+ * frame pairs of one sequence of F frames.  open3d's Odometry.cpp restated (parity
+ * with open3d itself is unpinned); what follows is the contract.  All P pairs
+ * advance together (the pair is a grid dimension), no host synchronisation between
+ * iterations; the call synchronises `stream` once at the end.  A pair's result is
+ * bitwise independent of the rest of the batch; two calls are bitwise equal.
+ *   Inputs     intensity, depth fp32 [F,H,W] (device; depth in metres, 0 =
+ *              invalid); pinhole fx, fy, cx, cy; pair_src, pair_tgt HOST int32 [P]
+ *              (checked on the host, copied on the stream); init device fp64
+ *              [P,16], NULL = identity; options on the host.
+ *   Outputs    trans [P,16] (source frame -> target frame), info [P,36], status [P].
+ *   1 frames   once per frame, fp32, shared by all pairs.  Depth d with d <
+ *              min_depth, d > max_depth or d <= 0 becomes NaN (open3d's test; the
+ *              bounds themselves stay).  Intensity and depth get a 3x3 Gaussian:
+ *              g(a, b, c) = (0.25 a + 0.5 b) + 0.25 c along u with clamped reads,
+ *              each row's value rounded to fp32, then the same along v; NaN
+ *              propagates.  Level l + 1 is the 2x2 mean (((p00 + p10) + p01) + p11)
+ *              0.25 (pXY: x = u offset) of level l; intensity is Gaussian-filtered
+ *              again before each downsample, depth is not.  Sobel with clamped
+ *              reads: dx = (h(v-1) + 2 h(v)) + h(v+1), h(v) = img(u+1, v) -
+ *              img(u-1, v); dy = (k(u-1) + 2 k(u)) + k(u+1), k(u) = img(u, v+1) -
+ *              img(u, v-1).  Level l's intrinsics are scaled by 2^-l (fp64).  The
+ *              xyz image is not stored: X = ((u - cx) d) / fx, Y likewise, Z = d in
+ *              fp64 from the fp32 depth where it is read (open3d stores fp32 xyz).
+ *   2 scales   a_s = 0.5 / mean I_s, a_t = 0.5 / mean I_t over the level-0
+ *              correspondences under init (fp64 sums of the fp32 values in f11's
+ *              fixed order); both 1 without a correspondence.  Every filter is
+ *              linear, so the scalars are applied where I and its gradients are read.
+ *   3 corr.    a source pixel i = v W + u with finite depth: p = R X + t (f12's
+ *              product order); needs p.z > 0; uf = (fx p.x) / p.z + cx + 0.5, vf
+ *              likewise; inside iff -1 < uf < W and -1 < vf < H; u_t = int(uf)
+ *              (truncation: uf in (-1, 0) is column 0, as open3d's cast); D_t(u_t,
+ *              v_t) finite and |p.z - D_t| <= max_depth_diff.  A target pixel keeps
+ *              the source pixel of the smallest p.z ROUNDED TO FP32, ties to the
+ *              lowest source index: one 64-bit atomic min on (fp32 bits of p.z,
+ *              source index) -- no order dependence.
+ *   4 rows     fp64 from the fp32 images; lambda_dep = 0.968, lambda_img = 1 -
+ *              lambda_dep, Sobel scale 0.125, NaN gradients count as 0.  r_I =
+ *              sqrt(lambda_img) (a_t I_t - a_s I_s), r_D = sqrt(lambda_dep) (D_t -
+ *              p.z).  c = 0.125 a_t (I_dx fx / p.z, I_dy fy / p.z) (target
+ *              gradients at (u_t, v_t)), c2 = -(c0 p.x + c1 p.y) / p.z: J_I =
+ *              sqrt(lambda_img) (-p.z c1 + p.y c2, p.z c0 - p.x c2, -p.y c0 + p.x
+ *              c1, c0, c1, c2); d likewise from the depth gradients (without a_t):
+ *              J_D = sqrt(lambda_dep) (-p.z d1 + p.y d2 - p.y, p.z d0 - p.x d2 +
+ *              p.x, -p.y d0 + p.x d1, d0, d1, d2 - 1).
+ *   5 solve    28 fp64 sums (J^T J's upper triangle row-major, J^T r, the count)
+ *              per 256-target-pixel chunk by xor shuffles and an LDS stage, then
+ *              over the chunks in order (f11's reduction; no float atomics).  J^T J
+ *              x = -J^T r by 6x6 Cholesky in one wave; T <- Exp(x) T with f12's Exp.
+ *              A pivot that is not positive and finite, a non-finite x, or zero
+ *              correspondences end that pair: success = 0, trans as last accepted.
+ *              iterations[k] iterations at level 2 - k (coarsest first).
+ *   6 info     over the level-0 correspondences under the final trans: f11's G^T G
+ *              of the back-projected target point ((u_t - cx) D_t / fx, .., D_t),
+ *              f11's reduction.  Zero without a correspondence.
+ *   Errors     PDSC_ERR_ARG on the host before any device work: null required
+ *              pointers, H or W below 8 or not divisible by 4, F < 1, P < 1, a pair
+ *              index outside [0, F) or src == tgt, intrinsics or max_depth_diff not
+ *              positive and finite, not 0 <= min_depth < max_depth, iterations
+ *              outside [0, 1000], a workspace that is too small.  F or P above
+ *              65535, or H W above 2^26: PDSC_ERR_UNSUPPORTED (the workspace query
+ *              returns 0).
+ * pdsc_rgbd_odometry_linearize is one linearisation by the same kernels: steps 1
+ * and 2 with `trans` as init, then at `level` the correspondence map corr
+ * [P, H_l W_l] (target pixel -> source pixel or -1; may be NULL), sums [P,28] (step
+ * 5's, in that order) and scales [P,2] = (a_s, a_t) (may be NULL).
+ * pdsc_rgbd_from_color_and_depth is open3d's create_from_color_and_depth: color
+ * uint8 [F,H,W,3], depth16 uint16 [F,H,W] -> intensity = ((0.299 R + 0.587 G) +
+ * 0.114 B) / 255 and depth = depth16 / depth_scale, 0 where that is above
+ * depth_trunc (fp32; asynchronous).                                          */
+typedef struct pdsc_rgbd_odometry_options { /* HOST; open3d's OdometryOption */
+    double  max_depth_diff;
+    double  min_depth;      /* open3d: 0 */
+    double  max_depth;      /* open3d: 4.0 */
+    int32_t iterations[3];  /* coarsest level first; open3d: 20, 10, 5 */
+    int32_t pad;
+} pdsc_rgbd_odometry_options;
+typedef struct pdsc_rgbd_odometry_status { /* device memory, one per pair */
+    int32_t success;
+    int32_t n_corr_last;    /* correspondences of the last linearisation */
+    int32_t iterations_run; /* accepted updates */
+    int32_t pad;
+} pdsc_rgbd_odometry_status;
+size_t  pdsc_rgbd_odometry_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t P);
+int32_t pdsc_rgbd_odometry(const float *intensity, const float *depth, int32_t F, int32_t H, int32_t W, double fx,
+                           double fy, double cx, double cy, const int32_t *pair_src, const int32_t *pair_tgt, int32_t P,
+                           const double *init, const pdsc_rgbd_odometry_options *options, double *trans, double *info,
+                           pdsc_rgbd_odometry_status *status, void *workspace, size_t workspace_bytes,
+                           pdsc_stream_t stream);
+int32_t pdsc_rgbd_odometry_linearize(const float *intensity, const float *depth, int32_t F, int32_t H, int32_t W,
+                                     double fx, double fy, double cx, double cy, const int32_t *pair_src,
+                                     const int32_t *pair_tgt, int32_t P, const double *trans,
+                                     const pdsc_rgbd_odometry_options *options, int32_t level, int32_t *corr,
+                                     double *sums, double *scales, void *workspace, size_t workspace_bytes,
+                                     pdsc_stream_t stream);
+int32_t pdsc_rgbd_from_color_and_depth(const uint8_t *color, const uint16_t *depth16, int32_t F, int32_t H, int32_t W,
+                                       double depth_scale, double depth_trunc, float *intensity, float *depth,
+                                       pdsc_stream_t stream);
+
+/* ------------------------------ f14 sparse TSDF volume (fragments) -----------
+ * open3d's ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) as multiway/
+ * make_fragments.py:116-139 uses it: integrate every frame, keep the vertices and
+ * vertex colours of extract_triangle_mesh (no triangles are built).  Restated;
+ * parity with open3d itself is unpinned.  ALL the state lives in one caller-owned
+ * device buffer, `workspace`, of pdsc_tsdf_workspace_bytes(max_blocks) bytes, that
+ * pdsc_tsdf_reset initialises; every call takes the same max_blocks.  Its first
+ * int32 is the number of blocks that own a pool slot.
+ *   Storage    blocks of 16^3 voxels, block edge = 16 voxel_length, block index =
+ *              floor(p / edge) per axis in [-2^20, 2^20) (else PDSC_ERR_UNSUPPORTED
+ *              after the call's synchronise); key = (bx + 2^20) << 42 | (by + 2^20)
+ *              << 21 | (bz + 2^20).  An open-addressing hash (>= 4 max_blocks
+ *              entries) from key to pool slot, insertion one 64-bit CAS, slots from
+ *              an atomic counter.  Per voxel (index x + 16 y + 256 z in its block):
+ *              tsdf, weight fp32, colour 3 x fp32 in 0 .. 255; 80 KB per block.
+ *   integrate  depth fp32 [H,W] metres, colour uint8 [H,W,3], extrinsic fp64 [16]
+ *              world -> camera (device).  Touch: every pixel (u, v) with u and v
+ *              multiples of 4 and depth > 0 is back-projected (((u - cx) d) / fx, ..,
+ *              d) and moved to the world by the extrinsic's inverse (R^T, -R^T t),
+ *              fp64, f12's product order; every block between floor((p - sdf_trunc)
+ *              / edge) and floor((p + sdf_trunc) / edge) per axis is inserted if
+ *              absent and marked touched.  Then ONLY the blocks this frame touched
+ *              are integrated, one workgroup each; per voxel: centre (idx + 0.5)
+ *              voxel_length to the camera; z > 0; uf = (fx x) / z + cx + 0.5, u =
+ *              int(uf) (f13's inside test); d = depth(u, v) > 0; sdf = (d - z)
+ *              sqrt((((u - cx) / fx)^2 + ((v - cy) / fy)^2) + 1) in fp64; if sdf >
+ *              -sdf_trunc: tsdf_new = (float) min(1, sdf / sdf_trunc), tsdf <- (tsdf
+ *              w + tsdf_new) / (w + 1) in fp32, each colour channel likewise, w <-
+ *              w + 1.  IEEE operations, no contraction.
+ *   Overflow   more blocks than max_blocks (or a full hash): PDSC_ERR_UNSUPPORTED
+ *              after the call's one final synchronise; that frame changes no voxel;
+ *              blocks that got a slot stay, at weight 0.
+ *   extraction a cube at voxel v is valid when all 8 corners v + {0,1}^3 exist and
+ *              have weight != 0 (a corner may lie in a neighbouring block).  The
+ *              edge (v, axis) from v to v + e_axis, f0 = tsdf(v), f1 = tsdf(v +
+ *              e_axis), is emitted once iff (f0 < 0) != (f1 < 0) and at least one of
+ *              its four adjacent cubes is valid.  Position (fp64): (idx + 0.5)
+ *              voxel_length with the axis coordinate moved by |f0| voxel_length /
+ *              (|f0| + |f1|); colour (|f1| c0 + |f0| c1) / (|f0| + |f1|) / 255.
+ *              Output in ascending (block key, voxel index, axis) order: slot
+ *              assignment never shows and two runs are bitwise equal.
+ *              pdsc_tsdf_count_surface_points returns the count (it synchronises);
+ *              the caller allocates points / colours fp64 [n,3] and calls
+ *              pdsc_tsdf_emit_surface_points with no integrate / write in between.
+ *   blocks     pdsc_tsdf_read_blocks copies the blocks out in slot order (coords
+ *              int32 [n,3], tsdf / weight [n,4096], colour [n,4096,3]; any may be
+ *              NULL; capacity >= the block count); pdsc_tsdf_write_blocks inserts
+ *              the given blocks (if absent) and overwrites their voxels -- a saved
+ *              volume, or a state a test fabricates.
+ *   Errors     PDSC_ERR_ARG on the host before any device work: null required
+ *              pointers, H or W < 1, intrinsics / voxel_length / sdf_trunc not
+ *              positive and finite, max_blocks < 1, a state buffer that is too
+ *              small; max_blocks > 2^17 (every count and offset of 3 x 4096
+ *              edges per block fits an int32): PDSC_ERR_UNSUPPORTED (the query
+ *              returns 0).  Two checks need the block / point count the buffer
+ *              holds and follow one synchronising read of it: read_blocks'
+ *              capacity < the block count and emit's capacity < the point count
+ *              (PDSC_ERR_ARG).  emit's points / colours must not be NULL.       */
+size_t  pdsc_tsdf_workspace_bytes(int32_t max_blocks);
+int32_t pdsc_tsdf_reset(int32_t max_blocks, void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+int32_t pdsc_tsdf_integrate(const float *depth, const uint8_t *colour, int32_t H, int32_t W, double fx, double fy,
+                            double cx, double cy, const double *extrinsic, double voxel_length, double sdf_trunc,
+                            int32_t max_blocks, void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+int32_t pdsc_tsdf_read_blocks(int32_t max_blocks, int32_t capacity, int32_t *coords, float *tsdf, float *weight,
+                              float *colour, void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+int32_t pdsc_tsdf_write_blocks(const int32_t *coords, int32_t n, const float *tsdf, const float *weight,
+                               const float *colour, int32_t max_blocks, void *workspace, size_t workspace_bytes,
+                               pdsc_stream_t stream);
+int32_t pdsc_tsdf_count_surface_points(int32_t max_blocks, int64_t *n_points /* HOST */, void *workspace,
+                                       size_t workspace_bytes, pdsc_stream_t stream);
+int32_t pdsc_tsdf_emit_surface_points(double voxel_length, int32_t max_blocks, double *points, double *colours,
+                                      int64_t capacity, void *workspace, size_t workspace_bytes, pdsc_stream_t stream);
+
 /* ------------------------------------------- f8 FCGF descriptors ----------
  * misc/fcgf.py's ResUNetBN2C(in_channels 1, out_channels C_out, conv1_kernel_size
  * 5 | 7, normalize_feature) in eval mode -- the sparse 3-D ResUNet that

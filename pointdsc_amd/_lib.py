@@ -135,6 +135,17 @@ class PdscPoseGraphResult(ctypes.Structure):
                 ("edges_kept", c_int32), ("solver_failed", c_int32)]
 
 
+class PdscRgbdOdometryOptions(ctypes.Structure):
+    """``struct pdsc_rgbd_odometry_options`` (include/pdsc.h): a host struct; open3d's OdometryOption."""
+    _fields_ = [("max_depth_diff", c_double), ("min_depth", c_double), ("max_depth", c_double),
+                ("iterations", c_int32 * 3), ("pad", c_int32)]
+
+
+class PdscRgbdOdometryStatus(ctypes.Structure):
+    """``struct pdsc_rgbd_odometry_status`` (include/pdsc.h): 16 bytes of device memory per pair."""
+    _fields_ = [("success", c_int32), ("n_corr_last", c_int32), ("iterations_run", c_int32), ("pad", c_int32)]
+
+
 class PdscFcgfDebug(ctypes.Structure):
     """``struct pdsc_fcgf_debug`` (include/pdsc.h): optional taps of pdsc_fcgf_forward."""
     _fields_ = [("block1", vp), ("block2", vp), ("block3", vp), ("block4", vp), ("block4_tr", vp), ("block3_tr", vp),
@@ -250,6 +261,21 @@ _PROTOS = {
                                            vp]),
     "pdsc_pose_graph_linearize": (c_int32, [vp, c_int32, vp, vp, vp, vp, vp, c_int32, vp, c_double, c_int32, vp, vp,
                                             vp, vp, vp, c_size_t, vp]),
+    "pdsc_rgbd_odometry_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "pdsc_rgbd_odometry": (c_int32, [vp, vp, c_int32, c_int32, c_int32, c_double, c_double, c_double, c_double, vp, vp,
+                                     c_int32, vp, vp, vp, vp, vp, vp, c_size_t, vp]),
+    "pdsc_rgbd_odometry_linearize": (c_int32, [vp, vp, c_int32, c_int32, c_int32, c_double, c_double, c_double,
+                                               c_double, vp, vp, c_int32, vp, vp, c_int32, vp, vp, vp, vp, c_size_t,
+                                               vp]),
+    "pdsc_rgbd_from_color_and_depth": (c_int32, [vp, vp, c_int32, c_int32, c_int32, c_double, c_double, vp, vp, vp]),
+    "pdsc_tsdf_workspace_bytes": (c_size_t, [c_int32]),
+    "pdsc_tsdf_reset": (c_int32, [c_int32, vp, c_size_t, vp]),
+    "pdsc_tsdf_integrate": (c_int32, [vp, vp, c_int32, c_int32, c_double, c_double, c_double, c_double, vp, c_double,
+                                      c_double, c_int32, vp, c_size_t, vp]),
+    "pdsc_tsdf_read_blocks": (c_int32, [c_int32, c_int32, vp, vp, vp, vp, vp, c_size_t, vp]),
+    "pdsc_tsdf_write_blocks": (c_int32, [vp, c_int32, vp, vp, vp, c_int32, vp, c_size_t, vp]),
+    "pdsc_tsdf_count_surface_points": (c_int32, [c_int32, vp, vp, c_size_t, vp]),
+    "pdsc_tsdf_emit_surface_points": (c_int32, [c_double, c_int32, vp, vp, ctypes.c_int64, vp, c_size_t, vp]),
     "pdsc_fcgf_param_floats": (c_size_t, [c_int32, c_int32]),
     "pdsc_fcgf_packed_floats": (c_size_t, [c_int32, c_int32]),
     "pdsc_fcgf_pack_weights": (c_int32, [vp, c_int32, c_int32, vp, vp]),

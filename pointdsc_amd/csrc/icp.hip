@@ -31,6 +31,7 @@
 
 #include "abi.hpp"
 #include "pdsc_common.hpp"
+#include "chunk_sums.hpp"
 #include "pdsc_internal.hpp"
 
 namespace pdsc {
@@ -122,24 +123,6 @@ PDSC_DEV IcpHit icp_nearest(const float *__restrict__ src, int i, const float *_
         }
     }
     return IcpHit{best, bd, qx, qy, qz, bx, by, bz};
-}
-
-// The fixed-order sum of a chunk's NS per-point values v (thread t of 256, all
-// of them calling together: it holds workgroup barriers): xor shuffles inside
-// each wave, the four waves' rows through red ([4][NS] of LDS) in wave order,
-// to part[NS chunk ..] (chunk < nchunks).
-template <int NS>
-PDSC_DEV void icp_reduce_chunk(const double (&v)[NS], int t, int chunk, int nchunks, double *red, double *part) {
-    const int w = t >> 6;
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        const double s = wave_sum(v[j]);
-        if ((t & 63) == 0) red[w * NS + j] = s;
-    }
-    __syncthreads();
-    if (t < NS && chunk < nchunks)
-        part[(size_t)chunk * NS + t] = ((red[t] + red[NS + t]) + red[2 * NS + t]) + red[3 * NS + t];
-    __syncthreads();  // red is free for the next chunk
 }
 
 // evaluate(T) for source chunk `chunk` (points 256 chunk + t, t = 0 .. 255, by
@@ -305,9 +288,8 @@ __global__ __launch_bounds__(ICP_WG) void icp_one_wg_kernel(const float *__restr
 // open3d's GetInformationMatrixFromPointClouds on evaluate(T)'s correspondences:
 // per correspondence the target point (x, y, z) in fp64, not transformed, adds
 // G^T G for G's rows (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1),
-// which is 10 sums: the count, sum t, and the six entries of sum t t^T.
-constexpr int INFO_NSUM = 10;  // count, x, y, z, xx, xy, xz, yy, yz, zz
-
+// which is 10 sums: the count, sum t, and the six entries of sum t t^T
+// (INFO_NSUM and info_from_sums, chunk_sums.hpp: f13 builds its matrix from them too).
 __global__ __launch_bounds__(ICP_CHUNK) void info_eval_kernel(const float *__restrict__ src, int Ns,
                                                               const float *__restrict__ tgt, const CloudStats *gs,
                                                               double cell, double r2, GridView g, const double *trans,
@@ -351,15 +333,8 @@ __global__ __launch_bounds__(64) void info_finish_kernel(const double *part, int
 #pragma unroll
     for (int j = 0; j < INFO_NSUM; ++j) S[j] = __shfl(acc, j);
     if (lane != 0) return;
-    const double n = S[0], x = S[1], y = S[2], z = S[3], xx = S[4], xy = S[5], xz = S[6], yy = S[7], yz = S[8],
-                 zz = S[9];
-    const double M[36] = {yy + zz, -xy, -xz, 0.0, -z,  y,    //
-                          -xy, xx + zz, -yz, z,   0.0, -x,   //
-                          -xz, -yz, xx + yy, -y,  x,   0.0,  //
-                          0.0, z,   -y,  n,   0.0, 0.0,      //
-                          -z,  0.0, x,   0.0, n,   0.0,      //
-                          y,   -x,  0.0, 0.0, 0.0, n};
-    for (int i = 0; i < 36; ++i) res->info[i] = n > 0.0 ? M[i] : 0.0;  // no correspondence: +0 everywhere
+    info_from_sums(S, res->info);
+    const double n = S[0];
     res->n_corr = (int)n;
     res->pad = 0;
 }

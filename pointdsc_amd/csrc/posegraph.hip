@@ -30,6 +30,7 @@
 #include "abi.hpp"
 #include "pdsc_common.hpp"
 #include "pdsc_internal.hpp"
+#include "se3.hpp"
 
 namespace pdsc {
 
@@ -75,30 +76,6 @@ static void bind_pg(Carve &c, int n, int E, PgBufs &W) {
     W.err = c.take<int>(1);
 }
 
-// ---- rigid transforms as their 3x4 part, row-major [12]; every product in the
-// order ((a0 b0 + a1 b1) + a2 b2) (+ a3), which the tests' restatement repeats
-PDSC_DEV void aff_load(const double *T, double (&A)[12]) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) A[i] = T[i];
-}
-PDSC_DEV void aff_inv(const double (&T)[12], double (&I)[12]) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) I[4 * r + c] = T[4 * c + r];
-        I[4 * r + 3] = -((I[4 * r] * T[3] + I[4 * r + 1] * T[7]) + I[4 * r + 2] * T[11]);
-    }
-}
-PDSC_DEV void aff_mul(const double (&A)[12], const double (&B)[12], double (&C)[12]) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const double s = (A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c];
-            C[4 * r + c] = c == 3 ? s + A[4 * r + 3] : s;
-        }
-    }
-}
 // open3d's TransformMatrix4dToVector6d, with its singular branch
 PDSC_DEV void vec6(const double (&M)[12], double (&v)[6]) {
     const double sy = sqrt(M[0] * M[0] + M[4] * M[4]);
@@ -454,11 +431,8 @@ PDSC_DEV void pg_trial(const double *poses, const double *delta, double *trial, 
     const int i = threadIdx.x;
     if (i < n) {
         const double *d = delta + 6 * i;
-        const double cx = cos(d[0]), sx = sin(d[0]), cy = cos(d[1]), sy = sin(d[1]), cz = cos(d[2]), sz = sin(d[2]);
-        const double Ex[12] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, d[3],  //
-                               sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, d[4],  //
-                               -sy,     cy * sx,                cy * cx,                d[5]};
-        double P[12], Q[12];
+        double Ex[12], P[12], Q[12];
+        se3_exp(d, Ex);
         aff_load(poses + 16 * (size_t)i, P);
         aff_mul(Ex, P, Q);
 #pragma unroll
