@@ -157,6 +157,29 @@ int32_t pdsc_attention_f32(const float *q, const float *k, const float *v, const
                            int32_t B, int32_t N, int32_t C, int32_t precision, float *msg, void *workspace,
                            size_t workspace_bytes, pdsc_stream_t stream);
 
+/* Training (no reference counterpart: autograd does this work there).  The same
+ * attention in exact fp32 -- msg is bit-equal to pdsc_attention_f32(...,
+ * PDSC_PRECISION_F32) on the same inputs -- that also writes the row
+ * log-sum-exp of the logits X_ij = M_ij q_i.k_j / sqrt(C): lse [B,N].  M must
+ * be symmetric and non-negative and carries no gradient.  C must be 128
+ * (else PDSC_ERR_ARG).                                                       */
+size_t pdsc_attention_lse_workspace_bytes(int32_t B, int32_t N, int32_t C);
+int32_t pdsc_attention_lse_f32(const float *q, const float *k, const float *v, const float *M,
+                               int32_t B, int32_t N, int32_t C, float *msg, float *lse, void *workspace,
+                               size_t workspace_bytes, pdsc_stream_t stream);
+/* Its backward: from the forward's inputs, msg and lse, and dmsg [B,N,C] = the
+ * gradient of a loss with respect to msg, the gradients dq, dk, dv [B,N,C].
+ * P_ij = exp(X_ij - lse_i) is recomputed tile by tile, never stored:
+ * D_i = dmsg_i.msg_i, dX_ij = P_ij (dmsg_i.v_j - D_i), dS_ij = M_ij dX_ij /
+ * sqrt(C), dq_i = sum_j dS_ij k_j, dk_j = sum_i dS_ij q_i, dv_j = sum_i P_ij
+ * dmsg_i.  fp32 throughout, no atomics: two calls on the same inputs are
+ * bit-equal.  C must be 128 (else PDSC_ERR_ARG).                            */
+size_t pdsc_attention_backward_workspace_bytes(int32_t B, int32_t N, int32_t C);
+int32_t pdsc_attention_backward_f32(const float *q, const float *k, const float *v, const float *M,
+                                    const float *msg, const float *lse, const float *dmsg, int32_t B, int32_t N,
+                                    int32_t C, float *dq, float *dk, float *dv, void *workspace,
+                                    size_t workspace_bytes, pdsc_stream_t stream);
+
 /* The TESTING / TRAINING FORWARD's attention geometry for (B, N): padded rows
  * per pair and the number of key splits (partials opart [B,nsplit,Npad,C],
  * ml [B,nsplit,Npad,2] in the forward workspace).  Both this query and

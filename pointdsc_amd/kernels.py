@@ -106,6 +106,38 @@ def attention(q, k, v, M, precision="h3"):
     return msg
 
 
+def _attention_args(q, k, v, M):
+    q, k, v, M = (_dev(t, n) for t, n in ((q, "q"), (k, "k"), (v, "v"), (M, "M")))
+    B, N, C = q.shape
+    if k.shape != q.shape or v.shape != q.shape or M.shape != (B, N, N):
+        raise ValueError(f"q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} M {tuple(M.shape)}")
+    return q, k, v, M, B, N, C
+
+
+def attention_lse(q, k, v, M):
+    """(msg [B,N,128], lse [B,N]): ``attention(..., precision='f32')`` bit for bit, and
+    the row log-sum-exp of the logits M_ij q_i.k_j / sqrt(C) its backward needs."""
+    q, k, v, M, B, N, C = _attention_args(q, k, v, M)
+    msg = torch.empty_like(q)
+    lse = torch.empty((B, N), dtype=torch.float32, device=q.device)
+    call("pdsc_attention_lse_f32", q, k, v, M, B, N, C, msg, lse, device=q.device,
+         ws=("pdsc_attention_lse_workspace_bytes", B, N, C))
+    return msg, lse
+
+
+def attention_backward(q, k, v, M, msg, lse, dmsg):
+    """(dq, dk, dv) [B,N,128] of ``attention_lse`` for the gradient dmsg of msg; the
+    softmax is recomputed from lse, not stored (include/pdsc.h).  M gets no gradient."""
+    q, k, v, M, B, N, C = _attention_args(q, k, v, M)
+    msg, lse, dmsg = _dev(msg, "msg"), _dev(lse, "lse"), _dev(dmsg, "dmsg")
+    if msg.shape != q.shape or dmsg.shape != q.shape or lse.shape != (B, N):
+        raise ValueError(f"msg {tuple(msg.shape)} dmsg {tuple(dmsg.shape)} lse {tuple(lse.shape)} for q {tuple(q.shape)}")
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    call("pdsc_attention_backward_f32", q, k, v, M, msg, lse, dmsg, B, N, C, dq, dk, dv, device=q.device,
+         ws=("pdsc_attention_backward_workspace_bytes", B, N, C))
+    return dq, dk, dv
+
+
 # ---------------------------------------------------------------------- a5
 def pick_seeds(src, conf, radius: float, max_num: int):
     """(seeds int32 [B,S], is_local_max [B,N]) (models/PointDSC.py:199-217)."""
