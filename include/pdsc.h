@@ -179,6 +179,23 @@ int32_t pdsc_attention_backward_f32(const float *q, const float *k, const float 
                                     const float *msg, const float *lse, const float *dmsg, int32_t B, int32_t N,
                                     int32_t C, float *dq, float *dk, float *dv, void *workspace,
                                     size_t workspace_bytes, pdsc_stream_t stream);
+/* SpectralMatchingLoss on the features, with its gradients, without an N x N
+ * tensor: normed [B,N,C] fp32 rows of unit length, sigma one device float,
+ * gt_labels [B,N] (0/1).  s_ij = n_i.n_j, u_ij = 1 - (1 - s_ij) / sigma^2,
+ * M_ij = clamp(u_ij, 0, 1), M_ii = 0, gt_ij = (l_i == 1 and l_j == 1 and i != j);
+ * balanced != 0 -> mean over pairs of 0.5 sum gt (M-1)^2 / P_b + 0.5 sum !gt
+ * M^2 / Q_b with P_b = max(k_b (k_b - 1) - 1, 0) + 1, Q_b = max(N^2 - k_b (k_b -
+ * 1) - 1, 0) + 1, k_b the pair's count of labels 1; else mean((M - gt)^2).
+ * loss: one device double.  dnormed [B,N,C] fp32 and dsigma (one device double)
+ * are dloss/dnormed and dloss/dsigma; both NULL computes the loss alone, one of
+ * them NULL is PDSC_ERR_ARG.  The clamp passes the gradient where 0 <= u <= 1
+ * (inclusive).  Sums in fp64, no atomics: two calls on the same inputs are
+ * bit-equal.  C must be 128 (else PDSC_ERR_UNSUPPORTED; the size query returns 0). */
+size_t pdsc_sm_loss_fused_workspace_bytes(int32_t B, int32_t N, int32_t C);
+int32_t pdsc_sm_loss_fused_f32(const float *normed, const float *sigma, const float *gt_labels, int32_t B, int32_t N,
+                               int32_t C, int32_t balanced, double *loss, float *dnormed /*nullable*/,
+                               double *dsigma /*nullable*/, void *workspace, size_t workspace_bytes,
+                               pdsc_stream_t stream);
 
 /* The TESTING / TRAINING FORWARD's attention geometry for (B, N): padded rows
  * per pair and the number of key splits (partials opart [B,nsplit,Npad,C],

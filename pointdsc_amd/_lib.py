@@ -176,6 +176,8 @@ _PROTOS = {
     "pdsc_attention_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "pdsc_attention_backward_f32": (c_int32, [vp, vp, vp, vp, vp, vp, vp, c_int32, c_int32, c_int32, vp, vp, vp, vp,
                                               c_size_t, vp]),
+    "pdsc_sm_loss_fused_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "pdsc_sm_loss_fused_f32": (c_int32, [vp, vp, vp, c_int32, c_int32, c_int32, c_int32, vp, vp, vp, vp, c_size_t, vp]),
     "pdsc_attention_layout": (c_int32, [c_int32, c_int32, c_int32, ctypes.POINTER(c_int32),
                                         ctypes.POINTER(c_int32)]),
     "pdsc_encoder_plan": (c_int32, [c_int32, c_int32, c_int32, ctypes.POINTER(c_int32)]),

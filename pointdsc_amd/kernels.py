@@ -138,6 +138,27 @@ def attention_backward(q, k, v, M, msg, lse, dmsg):
     return dq, dk, dv
 
 
+def sm_loss_fused(normed, sigma, gt_labels, balanced=True, grads=True):
+    """``(loss, dnormed | None, dsigma | None)``: SpectralMatchingLoss of the clamped
+    feature similarity of normed [B,N,128] (unit rows) and the device scalar sigma
+    against gt_labels [B,N], and d loss / d normed [B,N,128] fp32 and d loss / d sigma
+    (fp64 scalars, like the loss) from the same pass; no [B,N,N] tensor is made
+    (include/pdsc.h).  grads=False computes the loss alone."""
+    normed, gt = _dev(normed, "normed"), _dev(gt_labels, "gt_labels")
+    sigma = _dev(sigma.reshape(-1), "sigma")
+    if normed.dim() != 3 or gt.shape != normed.shape[:2] or sigma.numel() != 1:
+        raise ValueError(f"normed {tuple(normed.shape)} must be [B,N,C], gt_labels {tuple(gt.shape)} [B,N] and "
+                         f"sigma ({sigma.numel()} elements) a scalar")
+    B, N, C = normed.shape
+    dev = normed.device
+    loss = torch.empty((), dtype=torch.float64, device=dev)
+    dnormed = torch.empty_like(normed) if grads else None
+    dsigma = torch.empty((), dtype=torch.float64, device=dev) if grads else None
+    call("pdsc_sm_loss_fused_f32", normed, sigma, gt, B, N, C, int(bool(balanced)), loss, dnormed, dsigma, device=dev,
+         ws=("pdsc_sm_loss_fused_workspace_bytes", B, N, C))
+    return loss, dnormed, dsigma
+
+
 # ---------------------------------------------------------------------- a5
 def pick_seeds(src, conf, radius: float, max_num: int):
     """(seeds int32 [B,S], is_local_max [B,N]) (models/PointDSC.py:199-217)."""

@@ -3,7 +3,9 @@ forward only, on the gfx950 reduction kernels of ``libpdsc.so`` (fp64 sums).
 
 Used by the reference's validation loop (libs/trainer.py:237) on the ``M`` that
 ``PointDSC.forward`` returns without the 'testing' key.  There is no autograd
-through it (training proper is out of scope).
+through it: the loss to train with is ``pointdsc_amd.training.SpectralMatchingLoss``,
+which differentiates a dense M through torch ops and a ``FeatureSimilarity``
+through the fused kernel (DESIGN.md §7 "Training").
 """
 from __future__ import annotations
 

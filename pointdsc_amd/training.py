@@ -2,8 +2,12 @@
 attention of every NonLocal block, forward and backward, on the hand-written
 gfx950 kernels of ``libpdsc.so`` (csrc/attention_bwd.hip), and everything that
 is O(N C) -- the 1x1 convolutions, batch-statistics BatchNorm, ReLU, the
-classifier, ``F.normalize``, the feature-similarity M and the losses -- as torch
-ops (DESIGN.md §7 "Training").
+classifier, ``F.normalize`` and the classification loss -- as torch ops
+(DESIGN.md §7 "Training").  The feature-similarity M and its spectral-matching
+loss are torch ops on a [B,N,N] tensor by default; with ``model.dense_M = False``
+M stays a ``FeatureSimilarity`` (normed and sigma) and ``SpectralMatchingLoss``
+computes the loss and both gradients in one fused kernel
+(csrc/sm_loss_fused.hip) that stores nothing N x N.
 
 ``pointdsc_amd.PointDSC.PointDSC`` stays the inference module and keeps refusing
 ``model.train()``; train with ``TrainablePointDSC`` and move the weights across
@@ -59,6 +63,52 @@ def composed_attention(q, k, v, M):
     return torch.matmul(torch.softmax(M * S, dim=-1), v)
 
 
+class FeatureSimilarity:
+    """The feature-similarity M of models/PointDSC.py:158-163 held as its factors:
+    ``normed`` [B,N,C] and ``sigma``, with their autograd graphs.  ``dense()`` is
+    the [B,N,N] tensor; ``SpectralMatchingLoss`` takes the object itself and, on a
+    device, never builds that tensor."""
+
+    def __init__(self, normed, sigma):
+        self.normed, self.sigma = normed, sigma
+
+    @property
+    def shape(self):
+        B, N, _ = self.normed.shape
+        return torch.Size((B, N, N))
+
+    def dense(self):
+        M = torch.matmul(self.normed, self.normed.permute(0, 2, 1))
+        M = torch.clamp(1 - (1 - M) / self.sigma ** 2, min=0, max=1)
+        return M * (1 - torch.eye(M.shape[1], dtype=M.dtype, device=M.device))  # the diagonal := 0 (:163)
+
+
+class _FusedSpectralMatchingLoss(torch.autograd.Function):
+    """SpectralMatchingLoss(FeatureSimilarity(normed, sigma).dense(), gt_labels) on
+    the HIP kernel of csrc/sm_loss_fused.hip.  The upstream gradient of a scalar
+    is a scalar, so the forward's one pass also leaves d loss / d normed and
+    d loss / d sigma; the backward scales them.  ``grads`` False: the loss alone."""
+
+    @staticmethod
+    def forward(ctx, normed, sigma, gt_labels, balanced, grads):
+        loss, dnormed, dsigma = kernels.sm_loss_fused(normed.detach().float(), sigma.detach().float(),
+                                                      gt_labels.detach().float(), balanced, grads)
+        ctx.grads = grads
+        ctx.meta = (normed.dtype, sigma.dtype, sigma.shape)
+        if grads:
+            ctx.save_for_backward(dnormed, dsigma)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        if not ctx.grads:
+            raise RuntimeError("the fused spectral-matching loss was computed without gradients")
+        dnormed, dsigma = ctx.saved_tensors
+        ndt, sdt, sshape = ctx.meta
+        return ((dloss.to(dnormed.dtype) * dnormed).to(ndt), (dloss * dsigma).to(sdt).reshape(sshape),
+                None, None, None)
+
+
 class TrainablePointDSC(nn.Module):
     """models/PointDSC.py:80-197 for training: the reference's constructor
     arguments, parameter and buffer names (``state_dict()`` loads with
@@ -66,7 +116,8 @@ class TrainablePointDSC(nn.Module):
 
     ``forward(data)`` without the 'testing' key returns the reference's training
     branch: ``final_labels`` = the classifier logits, ``M`` = the clamped feature
-    similarity with a zero diagonal (both with autograd graphs), ``final_trans``
+    similarity with a zero diagonal (both with autograd graphs; M as a
+    ``FeatureSimilarity`` when ``self.dense_M`` is False), ``final_trans``
     [B,4,4] detached.  BatchNorm uses batch statistics and updates its running
     statistics while ``self.training``, and the running statistics in ``eval()``
     (the validation loop).  With 'testing' in ``data`` the call is delegated to an
@@ -100,12 +151,18 @@ class TrainablePointDSC(nn.Module):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 
-    def encode(self, corr_pos, compatibility, attention=nonlocal_attention):
+    # False: ``encode`` and ``forward`` return M as a ``FeatureSimilarity`` (no
+    # [B,N,N] tensor; SpectralMatchingLoss takes it on the fused kernel).  An
+    # attribute, not a constructor argument: the constructor stays the reference's.
+    dense_M = True
+
+    def encode(self, corr_pos, compatibility, attention=nonlocal_attention, dense_M=None):
         """(corr_features [B,N,C], normed [B,N,C], logits [B,N], M [B,N,N]) of
         models/PointDSC.py:155-163 and :171 from torch ops, the attention through
         ``attention(q, k, v, compatibility)`` on [B,N,C] rows.  ``attention`` is
         the hook the CPU tests use (``composed_attention``); nothing else here
-        needs a device."""
+        needs a device.  ``dense_M`` (None: ``self.dense_M``) False leaves M as
+        the ``FeatureSimilarity`` of normed and sigma."""
         enc = self.encoder
         feat = enc.layer0(corr_pos.permute(0, 2, 1))
         for i in range(enc.num_layers):
@@ -116,9 +173,9 @@ class TrainablePointDSC(nn.Module):
             feat = feat + blk.fc_message(message)
         features = feat.permute(0, 2, 1)
         normed = F.normalize(features, p=2, dim=-1)
-        M = torch.matmul(normed, normed.permute(0, 2, 1))
-        M = torch.clamp(1 - (1 - M) / self.sigma ** 2, min=0, max=1)
-        M = M * (1 - torch.eye(M.shape[1], dtype=M.dtype, device=M.device))  # the diagonal := 0 (:163)
+        M = FeatureSimilarity(normed, self.sigma)
+        if self.dense_M if dense_M is None else dense_M:
+            M = M.dense()
         logits = self.classification(features.permute(0, 2, 1)).squeeze(1)
         return features, normed, logits, M
 
@@ -212,13 +269,21 @@ class ClassificationLoss(nn.Module):
 class SpectralMatchingLoss(nn.Module):
     """libs/loss.py:115-139 in torch ops: gt_ij = (l_i + l_j == 2) with a zero
     diagonal; balanced: mean over pairs of half the positives' mean (M - 1)^2 plus
-    half the negatives' mean M^2; else mean((M - gt)^2).  Sums in fp64; an fp64 scalar."""
+    half the negatives' mean M^2; else mean((M - gt)^2).  Sums in fp64; an fp64 scalar.
+    M is a [B,N,N] tensor or a ``FeatureSimilarity``: the latter goes to the fused
+    kernel on a device (loss alone when nothing requires a gradient or under
+    ``no_grad``) and through ``dense()`` and the same ops on the CPU."""
 
     def __init__(self, balanced=True):
         super().__init__()
         self.balanced = balanced
 
     def forward(self, M, gt_labels):
+        if isinstance(M, FeatureSimilarity):
+            if M.normed.is_cuda:
+                grads = torch.is_grad_enabled() and (M.normed.requires_grad or M.sigma.requires_grad)
+                return _FusedSpectralMatchingLoss.apply(M.normed, M.sigma, gt_labels, self.balanced, grads)
+            M = M.dense()
         gt_labels = gt_labels.to(M.dtype)
         gt_M = ((gt_labels[:, None, :] + gt_labels[:, :, None]) == 2).to(M.dtype)
         gt_M = gt_M * (1 - torch.eye(M.shape[1], dtype=M.dtype, device=M.device))

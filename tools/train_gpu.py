@@ -8,7 +8,8 @@ correspondences, :74-79).  Prints the loss and the classification accuracy;
 writes the weights (an .npz of the state dict, loadable into
 pointdsc_amd.PointDSC.PointDSC) only to the path given with --out.
 
-    python tools/train_gpu.py {3dmatch,kitti} [--iters 400] [--layers 12] [--bs 16] [--num-node 1000] [--out W.npz]
+    python tools/train_gpu.py {3dmatch,kitti} [--iters 400] [--layers 12] [--bs 16] [--num-node 1000]
+                               [--fused_sm_loss] [--out W.npz]
 """
 import argparse
 import os
@@ -31,6 +32,8 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--weight-decay", type=float, default=1e-6)
     ap.add_argument("--balanced", action="store_true", help="the balanced forms of both losses")
+    ap.add_argument("--fused_sm_loss", action="store_true",
+                    help="the spectral-matching loss on the fused kernel: M is never built (model.dense_M = False)")
     ap.add_argument("--out", default=None, help="write the trained state dict here (.npz); nothing is written without it")
     a = ap.parse_args()
 
@@ -47,6 +50,7 @@ def main():
     init = synthetic_state_dict(a.layers, 128, seed=7, sigma_d=p["sigma_d"], cls_bias=0.0)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in init.items()}, strict=True)
     model = model.to(dev).train()
+    model.dense_M = not a.fused_sm_loss
     opt = torch.optim.Adam([q for q in model.parameters() if q.requires_grad], lr=a.lr, weight_decay=a.weight_decay)
     cls, sm = ClassificationLoss(balanced=a.balanced), SpectralMatchingLoss(balanced=a.balanced)
     rng = np.random.RandomState(1234)
