@@ -351,6 +351,9 @@ int32_t pdsc_spectral_matching(const float *corr_pos, const float *src, const fl
                                double inlier_threshold, double top_ratio, int32_t num_iterations, float *trans,
                                float *labels, float *leading_eig, void *workspace, size_t workspace_bytes,
                                pdsc_stream_t stream);
+/* The dense M [N,N] alone, by the launch pdsc_spectral_matching makes (exposed
+ * so that tests can see M): same limits on N and inlier_threshold.           */
+int32_t pdsc_sm_compat(const float *corr_pos, int32_t N, double inlier_threshold, float *M, pdsc_stream_t stream);
 /* One M v product of the SM power iteration (the HBM-bound kernel, exposed for
  * measurement): y [N] = M [N,N] v [N].                                       */
 int32_t pdsc_sm_matvec(const float *M, const float *v, int32_t N, float *y, pdsc_stream_t stream);

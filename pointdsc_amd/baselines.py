@@ -100,6 +100,23 @@ def GCRANSAC(corr, src_keypts, tgt_keypts, inlier_threshold: float = 0.10, max_i
     return pred_trans, res.labels[None]
 
 
+def sm_compat(corr, inlier_threshold: float = 0.10, out=None):
+    """SM's dense M [N,N] over corr [N,6] (baseline_3DMatch.py:20-36), by the
+    launch ``SM`` makes.  ``out``: a contiguous fp32 [N,N] device tensor to write
+    into (a view of a larger buffer lets a test put a guard row behind M)."""
+    corr = _dev(corr, "corr")
+    N = corr.shape[0]
+    if corr.shape != (N, 6):
+        raise ValueError(f"shape {tuple(corr.shape)}")
+    if out is None:
+        out = torch.empty((N, N), dtype=torch.float32, device=corr.device)
+    elif not (out.device == corr.device and out.dtype == torch.float32 and out.shape == (N, N)
+              and out.is_contiguous()):
+        raise ValueError("out: a contiguous fp32 [N,N] tensor on corr's device")
+    call("pdsc_sm_compat", corr, N, float(inlier_threshold), out, device=corr.device)
+    return out
+
+
 def sm_matvec(M, v):
     """y = M v (one SM power-iteration product; M [N,N], v [N])."""
     M, v = _dev(M, "M"), _dev(v, "v")

@@ -183,6 +183,21 @@ static void bind_sm(Carve &c, int N, SmBufs &W) {
     W.w = c.take<float>((size_t)N);
 }
 
+// what M accepts: N^2 elements within int32, a positive (not NaN) threshold
+static bool sm_compat_args_ok(int N, double inlier_threshold) {
+    return N >= 1 && N <= 46340 && inlier_threshold > 0.0;
+}
+
+// The one launch of sm_compat_kernel: the whole baseline and pdsc_sm_compat both
+// come through here.
+static hipError_t launch_sm_compat(const float *corr_pos, int N, double inlier_threshold, float *M, hipStream_t s) {
+    const double sigma = inlier_threshold / 3.0;  // :34 (python float)
+    const float sig2 = (float)(sigma * sigma);    // tensor / python scalar -> fp32 divisor
+    const int nt = (N + SM_T - 1) / SM_T;
+    hipLaunchKernelGGL(sm_compat_kernel, dim3(nt, nt), dim3(256), 0, s, corr_pos, N, sig2, M);
+    return hipGetLastError();
+}
+
 }  // namespace pdsc
 
 using namespace pdsc;
@@ -200,7 +215,7 @@ int32_t pdsc_spectral_matching(const float *corr_pos, const float *src, const fl
                                double inlier_threshold, double top_ratio, int32_t iters, float *trans,
                                float *labels, float *leading_eig, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
     if (!corr_pos || !src || !tgt || !trans || !labels || !ws) return fail(PDSC_ERR_ARG, "null pointer");
-    if (N < 1 || N > 46340 || iters < 0 || !(top_ratio >= 0.0 && top_ratio <= 1.0) || !(inlier_threshold > 0.0))
+    if (!sm_compat_args_ok(N, inlier_threshold) || iters < 0 || !(top_ratio >= 0.0 && top_ratio <= 1.0))
         return fail(PDSC_ERR_ARG, "N=%d iters=%d top_ratio=%g inlier_threshold=%g", N, iters, top_ratio,
                     inlier_threshold);
     RET_IF(need_ws(ws_bytes, pdsc_spectral_matching_workspace_bytes(N)));
@@ -209,12 +224,8 @@ int32_t pdsc_spectral_matching(const float *corr_pos, const float *src, const fl
     SmBufs W;
     bind_sm(c, N, W);
     float *M = W.M, *v = leading_eig ? leading_eig : W.v, *y = W.y, *w = W.w;
-    const double sigma = inlier_threshold / 3.0;  // :34 (python float)
-    const float sig2 = (float)(sigma * sigma);    // tensor / python scalar -> fp32 divisor
-    const int S = (int)(N * top_ratio);           // int(leading_eig.shape[1] * top_ratio) (:46)
-    const int nt = (N + SM_T - 1) / SM_T;
-    hipLaunchKernelGGL(sm_compat_kernel, dim3(nt, nt), dim3(256), 0, s, corr_pos, N, sig2, M);
-    HIPCHK(hipGetLastError());
+    const int S = (int)(N * top_ratio);  // int(leading_eig.shape[1] * top_ratio) (:46)
+    HIPCHK(launch_sm_compat(corr_pos, N, inlier_threshold, M, s));
     hipLaunchKernelGGL(sm_fill_kernel, dim3((N + 255) / 256), dim3(256), 0, s, v, N, 1.0f);  // :39
     for (int it = 0; it < iters; ++it) {
         hipLaunchKernelGGL(sm_matvec_kernel, dim3((N + 3) / 4), dim3(256), 0, s, M, v, N, y);
@@ -223,6 +234,14 @@ int32_t pdsc_spectral_matching(const float *corr_pos, const float *src, const fl
     hipLaunchKernelGGL(sm_select_kernel, dim3(1), dim3(1024), 0, s, v, N, S, labels, w);
     HIPCHK(hipGetLastError());
     HIPCHK(launch_rigid(src, tgt, w, 1, N, trans, s));
+    return PDSC_OK;
+}
+
+int32_t pdsc_sm_compat(const float *corr_pos, int32_t N, double inlier_threshold, float *M, pdsc_stream_t stream) {
+    if (!corr_pos || !M) return fail(PDSC_ERR_ARG, "null pointer");
+    if (!sm_compat_args_ok(N, inlier_threshold))
+        return fail(PDSC_ERR_ARG, "N=%d inlier_threshold=%g", N, inlier_threshold);
+    HIPCHK(launch_sm_compat(corr_pos, N, inlier_threshold, M, S_(stream)));
     return PDSC_OK;
 }
 

@@ -71,6 +71,10 @@ ENTRIES = {
         [{0: None}, {10: None}, {3: 0}, {3: 46341}, {6: -1}, {5: 1.5}, {5: "nan"}, {4: 0.0},
          {11: short("pdsc_spectral_matching_workspace_bytes", 100)}],
         [{8: None, 3: 0}, {6: -1, 11: short("pdsc_spectral_matching_workspace_bytes", 100)}]),
+    "pdsc_sm_compat": (
+        [P, 100, 0.1, P, None],
+        [{0: None}, {3: None}, {1: 0}, {1: 46341}, {2: 0.0}, {2: "nan"}],
+        [{0: None, 1: 0}, {1: 46341, 2: 0.0}]),
     "pdsc_sm_matvec": (
         [P, P, 10, P, None],
         [{0: None}, {3: None}, {2: 0}],
