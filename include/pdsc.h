@@ -1303,6 +1303,15 @@ int32_t pdsc_rgbd_from_color_and_depth(const uint8_t *color, const uint16_t *dep
  *   Overflow   more blocks than max_blocks (or a full hash): PDSC_ERR_UNSUPPORTED
  *              after the call's one final synchronise; that frame changes no voxel;
  *              blocks that got a slot stay, at weight 0.
+ *   Range      a block index outside [-2^20, 2^20) or a non-finite point, in
+ *              integrate or write_blocks: PDSC_ERR_UNSUPPORTED likewise; the call
+ *              changes no voxel and NO block gets a slot, so the block count and
+ *              every block read back are as before the call.  The keys the failed
+ *              call named keep their hash entries without a slot, as the surplus
+ *              keys of an overflow do (open addressing cannot delete): a later
+ *              call finds and reuses them, but calls that keep failing on FRESH
+ *              blocks can use up the 4 max_blocks entries, and the volume then
+ *              reports "full" below max_blocks blocks until pdsc_tsdf_reset.
  *   extraction a cube at voxel v is valid when all 8 corners v + {0,1}^3 exist and
  *              have weight != 0 (a corner may lie in a neighbouring block).  The
  *              edge (v, axis) from v to v + e_axis, f0 = tsdf(v), f1 = tsdf(v +

@@ -213,6 +213,7 @@ __global__ void tsdf_touch_list_kernel(TsdfBufs B, const int *__restrict__ coord
 __global__ __launch_bounds__(TSDF_WG) void tsdf_alloc_kernel(TsdfBufs B, int max_blocks) {
     const int h = blockIdx.x * TSDF_WG + threadIdx.x;
     if (h >= B.hash_cap || B.hstamp[h] != B.hdr->frame) return;
+    if (B.hdr->status & TSDF_ERR_RANGE) return;  // a range error: no block gets a slot, the volume is as it was
     int slot = B.hvals[h];
     if (slot < 0) {
         slot = atomicAdd(&B.hdr->counter, 1);

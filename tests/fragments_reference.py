@@ -219,96 +219,218 @@ def block_key(c):
     return (c[..., 0] << 42) | (c[..., 1] << 21) | c[..., 2]
 
 
+class TsdfError(RuntimeError):
+    """The library's PDSC_ERR_UNSUPPORTED of f14: "outside" (a block index) or "full"."""
+
+
+def _range_check(lo, hi):
+    if not (np.all(lo >= -(1 << 20)) and np.all(hi < (1 << 20))):  # also NaN
+        raise TsdfError("a block index outside [-2^20, 2^20) (or a non-finite point)")
+
+
 class Volume:
-    """blocks: {(bx, by, bz): [tsdf fp32 [4096], weight fp32 [4096], colour fp32 [4096,3]]}, voxel x + 16 y + 256 z."""
+    """blocks: {(bx, by, bz): [tsdf fp32 [4096], weight fp32 [4096], colour fp32 [4096,3]]}, voxel x + 16 y + 256 z.
+
+    Each rule of the contract is one small method, so that a test can derive a volume with
+    one rule broken and show that its assertions tell the two apart.  `stats` counts, over
+    all integrate calls, the voxels that went through each branch of the inside test."""
 
     def __init__(self, voxel_length, sdf_trunc, max_blocks=1 << 19):
         self.vl, self.trunc, self.max_blocks = float(voxel_length), float(sdf_trunc), max_blocks
         self.blocks = {}
+        self.stats = dict.fromkeys(("integrated", "u_neg", "v_neg", "u_out", "pz_le0", "sdf_eq_lo", "sdf_eq_hi",
+                                    "sdf_gt_hi"), 0)
+        self.last_keys = np.zeros((0, 3), np.int64)  # of the last extract(): (block key, voxel index, axis) per point
 
-    def touched(self, depth, K, extrinsic):
-        fx, fy, cx, cy = K
-        Ei = aff_inv(np.asarray(extrinsic, dtype=np.float64))
-        v, u = np.meshgrid(np.arange(0, depth.shape[0], 4), np.arange(0, depth.shape[1], 4), indexing="ij")
-        d = depth[v, u].astype(np.float64)
-        m = d > 0
-        u, v, d = u[m].astype(np.float64), v[m].astype(np.float64), d[m]
-        p = np.stack(apply_T(Ei, ((u - cx) * d) / fx, ((v - cy) * d) / fy, d), 1)
-        edge = self.vl * B
-        lo, hi = np.floor((p - self.trunc) / edge).astype(np.int64), np.floor((p + self.trunc) / edge).astype(np.int64)
-        out = set()
-        for a, b in zip(lo, hi):
-            for bx in range(a[0], b[0] + 1):
-                for by in range(a[1], b[1] + 1):
-                    for bz in range(a[2], b[2] + 1):
-                        out.add((bx, by, bz))
-        return out
+    # ---- the rules
+    def sample_grid(self, H, W):
+        return np.arange(0, H, 4), np.arange(0, W, 4)
 
-    def integrate(self, depth, colour, K, extrinsic):
-        """False (and no change) when the frame needs more than max_blocks blocks."""
-        fx, fy, cx, cy = K
-        E = np.asarray(extrinsic, dtype=np.float64)
-        H, W = depth.shape
-        touched = self.touched(depth, K, E)
-        if len(set(self.blocks) | touched) > self.max_blocks:
-            return False
-        vi = np.arange(B ** 3)
-        off = np.stack([vi & 15, (vi >> 4) & 15, vi >> 8], 1)
-        for key in touched:
-            blk = self.blocks.setdefault(key, [np.zeros(B ** 3, f32), np.zeros(B ** 3, f32), np.zeros((B ** 3, 3), f32)])
-            w = ((np.array(key) * B + off).astype(np.float64) + 0.5) * self.vl
-            px, py, pz = apply_T(E, w[:, 0], w[:, 1], w[:, 2])
-            with np.errstate(invalid="ignore", divide="ignore"):
-                uf, vf = (fx * px) / pz + cx + 0.5, (fy * py) / pz + cy + 0.5
-                ok = (pz > 0) & (uf > -1.0) & (uf < W) & (vf > -1.0) & (vf < H)
-            u, v = np.where(ok, uf, 0).astype(np.int64), np.where(ok, vf, 0).astype(np.int64)
-            d = depth[v, u]
-            ok &= d > 0
-            rx, ry = (u - cx) / fx, (v - cy) / fy
-            sdf = (d.astype(np.float64) - pz) * np.sqrt((rx * rx + ry * ry) + 1.0)
-            ok &= sdf > -self.trunc
-            tn = np.minimum(1.0, sdf / self.trunc).astype(f32)
-            t, wt, col = blk
-            w1 = wt + f32(1)
-            t[ok] = ((t * wt + tn) / w1)[ok]
-            col[ok] = ((col * wt[:, None] + colour[v, u].astype(f32)) / w1[:, None])[ok]
-            wt[ok] = w1[ok]
-        return True
+    def pixel(self, xf):
+        return xf.astype(np.int64)  # truncation
 
-    def sorted_blocks(self):
-        keys = sorted(self.blocks, key=lambda c: int(block_key(c)))
-        return (np.array(keys, dtype=np.int32).reshape(-1, 3), np.stack([self.blocks[k][0] for k in keys]),
-                np.stack([self.blocks[k][1] for k in keys]), np.stack([self.blocks[k][2] for k in keys]))
+    def keep(self, sdf):
+        return sdf > -self.trunc
 
-    def extract(self):
-        """(points [n,3], colours [n,3], fsum [n] = |f0| + |f1|) in (block key, voxel
-        index, axis) order, straight from the definition on a dense grid: an edge is
-        emitted iff its ends differ in sign and one of its four cubes is valid."""
-        if not self.blocks:
-            return np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0)
-        keys = np.array(list(self.blocks), dtype=np.int64)
-        lo = keys.min(0) - 1
-        n = (keys.max(0) - lo + 2) * B
-        F, Wt, C = np.zeros(n, f32), np.zeros(n, f32), np.zeros(tuple(n) + (3,), f32)
-        for k, (t, w, c) in self.blocks.items():
-            o = (np.array(k) - lo) * B
-            sl = tuple(slice(o[a], o[a] + B) for a in range(3))
-            F[sl] = t.reshape(B, B, B).transpose(2, 1, 0)  # [x, y, z] from index x + 16 y + 256 z
-            Wt[sl] = w.reshape(B, B, B).transpose(2, 1, 0)
-            C[sl] = c.reshape(B, B, B, 3).transpose(2, 1, 0, 3)
-        nz = Wt != 0
+    def integration_set(self, touched):
+        return touched
+
+    def negative(self, F):
+        return F < 0
+
+    def cube_valid(self, nz):
+        """cube[v]: all 8 corners v + {0,1}^3 have weight != 0 (on the dense grid; absent blocks are 0)."""
+        n = nz.shape
         cube = np.zeros(n, bool)
         cube[:-1, :-1, :-1] = True
         for dx in (0, 1):
             for dy in (0, 1):
                 for dz in (0, 1):
                     cube[:-1, :-1, :-1] &= nz[dx:n[0] - 1 + dx, dy:n[1] - 1 + dy, dz:n[2] - 1 + dz]
-        neg = F < 0
+        return cube
+
+    def edge_alive(self, cube, o1, o2):
+        """any of the four cubes around the edge (v, a): v - {0,1} e_o1 - {0,1} e_o2"""
+        return cube | np.roll(cube, 1, o1) | np.roll(cube, 1, o2) | np.roll(np.roll(cube, 1, o1), 1, o2)
+
+    def block_rank(self, blk):
+        return block_key(blk)
+
+    # ---- f14
+    def _zeros(self):
+        return [np.zeros(B ** 3, f32), np.zeros(B ** 3, f32), np.zeros((B ** 3, 3), f32)]
+
+    def touched(self, depth, K, extrinsic):
+        fx, fy, cx, cy = K
+        Ei = aff_inv(np.asarray(extrinsic, dtype=np.float64))
+        vs, us = self.sample_grid(*depth.shape)
+        v, u = np.meshgrid(vs, us, indexing="ij")
+        d = depth[v, u].astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            m = d > 0
+        u, v, d = u[m].astype(np.float64), v[m].astype(np.float64), d[m]
+        with np.errstate(invalid="ignore", over="ignore"):
+            p = np.stack(apply_T(Ei, ((u - cx) * d) / fx, ((v - cy) * d) / fy, d), 1)
+            edge = self.vl * B
+            lo, hi = np.floor((p - self.trunc) / edge), np.floor((p + self.trunc) / edge)
+        _range_check(lo, hi)
+        out = set()
+        for a, b in zip(lo.astype(np.int64), hi.astype(np.int64)):
+            for bx in range(a[0], b[0] + 1):
+                for by in range(a[1], b[1] + 1):
+                    for bz in range(a[2], b[2] + 1):
+                        out.add((bx, by, bz))
+        return out
+
+    def integrate(self, depth, colour, K, extrinsic, slotted=None):
+        """False when the frame needs more than max_blocks blocks: no voxel changes, and as
+        many of the frame's new blocks as there are free slots come into being at weight 0 --
+        on the GPU whichever win the race (`slotted`: those, as read back), here the lowest
+        keys.  TsdfError, and no change at all, at a block index out of range."""
+        fx, fy, cx, cy = K
+        E = np.asarray(extrinsic, dtype=np.float64)
+        H, W = depth.shape
+        touched = self.touched(depth, K, E)
+        new = touched - set(self.blocks)
+        if len(self.blocks) + len(new) > self.max_blocks:
+            room = self.max_blocks - len(self.blocks)
+            take = sorted(new, key=lambda c: int(block_key(c)))[:room] if slotted is None else [tuple(k) for k in slotted]
+            assert set(take) <= new and len(set(take)) == room, "the slotted blocks are not the frame's"
+            for key in take:
+                self.blocks[key] = self._zeros()
+            return False
+        for key in new:
+            self.blocks[key] = self._zeros()
+        vi = np.arange(B ** 3)
+        off = np.stack([vi & 15, (vi >> 4) & 15, vi >> 8], 1)
+        st = self.stats
+        for key in self.integration_set(touched):
+            blk = self.blocks[key]
+            w = ((np.array(key) * B + off).astype(np.float64) + 0.5) * self.vl
+            px, py, pz = apply_T(E, w[:, 0], w[:, 1], w[:, 2])
+            with np.errstate(invalid="ignore", divide="ignore"):
+                uf, vf = (fx * px) / pz + cx + 0.5, (fy * py) / pz + cy + 0.5
+                front = pz > 0
+                ok = front & (uf > -1.0) & (uf < W) & (vf > -1.0) & (vf < H)
+                st["pz_le0"] += int((~front).sum())
+                st["u_out"] += int((front & ((uf <= -1.0) | (uf >= W))).sum())
+                u, v = self.pixel(np.where(ok, uf, 0)), self.pixel(np.where(ok, vf, 0))
+                d = depth[v, u]
+                ok &= d > 0
+                rx, ry = (u - cx) / fx, (v - cy) / fy
+                sdf = (d.astype(np.float64) - pz) * np.sqrt((rx * rx + ry * ry) + 1.0)
+                st["sdf_eq_lo"] += int((ok & (sdf == -self.trunc)).sum())
+                ok &= self.keep(sdf)
+                tn = np.minimum(1.0, sdf / self.trunc).astype(f32)
+            st["integrated"] += int(ok.sum())
+            st["u_neg"] += int((ok & (uf < 0)).sum())
+            st["v_neg"] += int((ok & (vf < 0)).sum())
+            st["sdf_eq_hi"] += int((ok & (sdf == self.trunc)).sum())
+            st["sdf_gt_hi"] += int((ok & (sdf > self.trunc)).sum())
+            t, wt, col = blk
+            w1 = wt + f32(1)
+            with np.errstate(invalid="ignore"):
+                t[ok] = ((t * wt + tn) / w1)[ok]
+                col[ok] = ((col * wt[:, None] + colour[v, u].astype(f32)) / w1[:, None])[ok]
+            wt[ok] = w1[ok]
+        return True
+
+    def write_blocks(self, coords, tsdf, weight, colour):
+        """pdsc_tsdf_write_blocks: TsdfError "outside" with no change at all; "full" with no
+        voxel written, the free slots filled from the new blocks (here: in the given order)."""
+        coords = np.asarray(coords, dtype=np.int64).reshape(-1, 3)
+        _range_check(coords, coords)
+        keys = [tuple(int(x) for x in c) for c in coords]
+        new = [k for k in dict.fromkeys(keys) if k not in self.blocks]
+        if len(self.blocks) + len(new) > self.max_blocks:
+            for k in new[:self.max_blocks - len(self.blocks)]:
+                self.blocks[k] = self._zeros()
+            raise TsdfError(f"the volume is full: more than max_blocks={self.max_blocks} blocks")
+        for i, k in enumerate(keys):
+            self.blocks[k] = [np.array(tsdf[i], f32), np.array(weight[i], f32), np.array(colour[i], f32).reshape(-1, 3)]
+
+    def sorted_blocks(self):
+        keys = sorted(self.blocks, key=lambda c: int(block_key(c)))
+        if not keys:
+            return (np.zeros((0, 3), np.int32), np.zeros((0, B ** 3), f32), np.zeros((0, B ** 3), f32),
+                    np.zeros((0, B ** 3, 3), f32))
+        return (np.array(keys, dtype=np.int32).reshape(-1, 3), np.stack([self.blocks[k][0] for k in keys]),
+                np.stack([self.blocks[k][1] for k in keys]), np.stack([self.blocks[k][2] for k in keys]))
+
+    def extract(self):
+        """(points [n,3], colours [n,3], fsum [n] = |f0| + |f1|) in (block key, voxel
+        index, axis) order, straight from the definition on a dense grid: an edge is
+        emitted iff its ends differ in sign and one of its four cubes is valid.  The grid
+        is the bounding box of each 26-connected group of blocks (a cube never spans two
+        groups), so far-apart blocks cost nothing."""
+        self.last_keys = np.zeros((0, 3), np.int64)
+        recs = []
+        for group in self._groups():
+            recs += self._extract_group(group)
+        if not recs:
+            return np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0)
+        ok = np.concatenate([r[0] for r in recs])
+        rank = np.concatenate([r[4] for r in recs])
+        order = np.lexsort((ok[:, 2], ok[:, 1], rank))
+        self.last_keys = ok[order]
+        return (np.concatenate([r[1] for r in recs])[order], np.concatenate([r[2] for r in recs])[order],
+                np.concatenate([r[3] for r in recs])[order])
+
+    def _groups(self):
+        left, groups = set(self.blocks), []
+        while left:
+            stack, group = [left.pop()], []
+            while stack:
+                k = stack.pop()
+                group.append(k)
+                for dx in (-1, 0, 1):
+                    for dy in (-1, 0, 1):
+                        for dz in (-1, 0, 1):
+                            q = (k[0] + dx, k[1] + dy, k[2] + dz)
+                            if q in left:
+                                left.remove(q)
+                                stack.append(q)
+            groups.append(group)
+        return groups
+
+    def _extract_group(self, group):
+        keys = np.array(group, dtype=np.int64)
+        lo = keys.min(0) - 1
+        n = (keys.max(0) - lo + 2) * B
+        F, Wt, C = np.zeros(n, f32), np.zeros(n, f32), np.zeros(tuple(n) + (3,), f32)
+        for k in group:
+            t, w, c = self.blocks[k]
+            o = (np.array(k) - lo) * B
+            sl = tuple(slice(o[a], o[a] + B) for a in range(3))
+            F[sl] = t.reshape(B, B, B).transpose(2, 1, 0)  # [x, y, z] from index x + 16 y + 256 z
+            Wt[sl] = w.reshape(B, B, B).transpose(2, 1, 0)
+            C[sl] = c.reshape(B, B, B, 3).transpose(2, 1, 0, 3)
+        cube = self.cube_valid(Wt != 0)
+        neg = self.negative(F)
         recs = []
         for a in range(3):
             o1, o2 = [x for x in range(3) if x != a]
-            near = cube.copy()  # any of the four cubes around the edge (v, a): v - {0,1} e_o1 - {0,1} e_o2
-            near |= np.roll(cube, 1, o1) | np.roll(cube, 1, o2) | np.roll(np.roll(cube, 1, o1), 1, o2)
+            near = self.edge_alive(cube, o1, o2)
             sign = neg != np.roll(neg, -1, a)
             idx = np.argwhere(sign & near)
             if not len(idx):
@@ -324,13 +446,8 @@ class Volume:
                 / (f0 + f1)[:, None] / 255.0
             blk, v = g // B, g % B
             order_key = np.stack([block_key(blk), v[:, 0] + 16 * v[:, 1] + 256 * v[:, 2], np.full(len(g), a)], 1)
-            recs.append((order_key, p, col, f0 + f1))
-        if not recs:
-            return np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0)
-        ok = np.concatenate([r[0] for r in recs])
-        order = np.lexsort((ok[:, 2], ok[:, 1], ok[:, 0]))
-        return (np.concatenate([r[1] for r in recs])[order], np.concatenate([r[2] for r in recs])[order],
-                np.concatenate([r[3] for r in recs])[order])
+            recs.append((order_key, p, col, f0 + f1, np.asarray(self.block_rank(blk))))
+        return recs
 
 
 # ------------------------------------------------------------------ scenes

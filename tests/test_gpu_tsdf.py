@@ -10,6 +10,7 @@ import torch
 
 import fragments_reference as R
 from pointdsc_amd import fragments as F
+from tsdf_edge_cases import assert_blocks_equal as _assert_blocks_equal  # the bars, shared with test_gpu_tsdf_edges.py
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +22,6 @@ POSE0 = R.exp6(np.array([0.02, -0.03, 0.01, -0.3, -0.2, -2.0]))
 
 def _t(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _ulps(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64)).max()
 
 
 def _frames(n):
@@ -47,14 +43,6 @@ def _integrate_both(dev, n, max_blocks=2048):
         vol.integrate(_t(d, dev), _t(c, dev), K, _t(E, dev))
         snaps.append((touched, before, vol.blocks()))
     return ref, vol, snaps
-
-
-def _assert_blocks_equal(got, ref):
-    coords, tsdf, weight, colour = (x.cpu().numpy() for x in got)
-    rc, rt, rw, rcol = ref.sorted_blocks()
-    assert np.array_equal(coords, rc)
-    assert np.array_equal(weight.view(np.int32), rw.view(np.int32))
-    assert _ulps(tsdf, rt) <= 2 and _ulps(colour, rcol) <= 2
 
 
 def test_one_frame(gpu_device):
