@@ -1223,7 +1223,9 @@ int32_t pdsc_pose_graph_linearize(const double *poses, int32_t n, const int32_t 
  *              x = -J^T r by 6x6 Cholesky in one wave; T <- Exp(x) T with f12's Exp.
  *              A pivot that is not positive and finite, a non-finite x, or zero
  *              correspondences end that pair: success = 0, trans as last accepted.
- *              iterations[k] iterations at level 2 - k (coarsest first).
+ *              iterations[k] iterations at level 2 - k (coarsest first).  success
+ *              = no iteration failed: with iterations = (0, 0, 0) it is 1,
+ *              n_corr_last and iterations_run are 0 and trans is init bit for bit.
  *   6 info     over the level-0 correspondences under the final trans: f11's G^T G
  *              of the back-projected target point ((u_t - cx) D_t / fx, .., D_t),
  *              f11's reduction.  Zero without a correspondence.
@@ -1238,6 +1240,10 @@ int32_t pdsc_pose_graph_linearize(const double *poses, int32_t n, const int32_t 
  * and 2 with `trans` as init, then at `level` the correspondence map corr
  * [P, H_l W_l] (target pixel -> source pixel or -1; may be NULL), sums [P,28] (step
  * 5's, in that order) and scales [P,2] = (a_s, a_t) (may be NULL).
+ * pdsc_rgbd_odometry_pyramid is step 1 alone, by the same launches and frame
+ * checks (exposed so that tests can see the images): level `level` of all F
+ * frames into six device fp32 arrays [F, H_l, W_l], each may be NULL; workspace of
+ * pdsc_rgbd_odometry_workspace_bytes(F, H, W, 1).
  * pdsc_rgbd_from_color_and_depth is open3d's create_from_color_and_depth: color
  * uint8 [F,H,W,3], depth16 uint16 [F,H,W] -> intensity = ((0.299 R + 0.587 G) +
  * 0.114 B) / 255 and depth = depth16 / depth_scale, 0 where that is above
@@ -1267,6 +1273,10 @@ int32_t pdsc_rgbd_odometry_linearize(const float *intensity, const float *depth,
                                      const pdsc_rgbd_odometry_options *options, int32_t level, int32_t *corr,
                                      double *sums, double *scales, void *workspace, size_t workspace_bytes,
                                      pdsc_stream_t stream);
+int32_t pdsc_rgbd_odometry_pyramid(const float *intensity, const float *depth, int32_t F, int32_t H, int32_t W,
+                                   double min_depth, double max_depth, int32_t level, float *I, float *D, float *Idx,
+                                   float *Idy, float *Ddx, float *Ddy, void *workspace, size_t workspace_bytes,
+                                   pdsc_stream_t stream);
 int32_t pdsc_rgbd_from_color_and_depth(const uint8_t *color, const uint16_t *depth16, int32_t F, int32_t H, int32_t W,
                                        double depth_scale, double depth_trunc, float *intensity, float *depth,
                                        pdsc_stream_t stream);

@@ -275,6 +275,8 @@ _PROTOS = {
     "pdsc_rgbd_odometry_linearize": (c_int32, [vp, vp, c_int32, c_int32, c_int32, c_double, c_double, c_double,
                                                c_double, vp, vp, c_int32, vp, vp, c_int32, vp, vp, vp, vp, c_size_t,
                                                vp]),
+    "pdsc_rgbd_odometry_pyramid": (c_int32, [vp, vp, c_int32, c_int32, c_int32, c_double, c_double, c_int32, vp, vp, vp,
+                                             vp, vp, vp, vp, c_size_t, vp]),
     "pdsc_rgbd_from_color_and_depth": (c_int32, [vp, vp, c_int32, c_int32, c_int32, c_double, c_double, vp, vp, vp]),
     "pdsc_tsdf_workspace_bytes": (c_size_t, [c_int32]),
     "pdsc_tsdf_reset": (c_int32, [c_int32, vp, c_size_t, vp]),

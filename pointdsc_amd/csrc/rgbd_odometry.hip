@@ -467,10 +467,14 @@ static void bind_odo(Carve &c, int F, int H, int W, int P, OdoBufs &B) {
     B.pair_tgt = c.take<int>(P);
 }
 
+// One predicate for every entry.  frames_only (the pyramid entry: step 1 has no
+// pairs) leaves out the checks of the pair list, the intrinsics, max_depth_diff
+// and the iteration counts; the frame checks and their order are the same.
 static int odo_check(const void *intensity, const void *depth, int F, int H, int W, double fx, double fy, double cx,
                      double cy, const int32_t *pair_src, const int32_t *pair_tgt, int P,
-                     const pdsc_rgbd_odometry_options *opt, const void *ws) {
-    if (!intensity || !depth || !pair_src || !pair_tgt || !opt || !ws) return fail(PDSC_ERR_ARG, "null pointer");
+                     const pdsc_rgbd_odometry_options *opt, const void *ws, bool frames_only = false) {
+    if (!intensity || !depth || (!frames_only && (!pair_src || !pair_tgt)) || !opt || !ws)
+        return fail(PDSC_ERR_ARG, "null pointer");
     if (F < 1 || P < 1) return fail(PDSC_ERR_ARG, "F=%d P=%d (need F >= 1, P >= 1)", F, P);
     if (H < 8 || W < 8 || H % 4 || W % 4)
         return fail(PDSC_ERR_ARG, "H=%d W=%d (need >= 8 and divisible by 4: three pyramid levels)", H, W);
@@ -480,13 +484,14 @@ static int odo_check(const void *intensity, const void *depth, int F, int H, int
         return fail(PDSC_ERR_UNSUPPORTED, "H=%d W=%d (at most 2^26 pixels per frame)", H, W);
     const double k[4] = {fx, fy, cx, cy};
     for (double v : k)
-        if (!(v > 0.0) || !std::isfinite(v))
+        if (!frames_only && (!(v > 0.0) || !std::isfinite(v)))
             return fail(PDSC_ERR_ARG, "intrinsics fx=%g fy=%g cx=%g cy=%g must be > 0 and finite", fx, fy, cx, cy);
-    if (!(opt->max_depth_diff > 0.0) || !std::isfinite(opt->max_depth_diff))
+    if (!frames_only && (!(opt->max_depth_diff > 0.0) || !std::isfinite(opt->max_depth_diff)))
         return fail(PDSC_ERR_ARG, "max_depth_diff %g must be > 0 and finite", opt->max_depth_diff);
     if (!(opt->min_depth >= 0.0) || !(opt->max_depth > opt->min_depth) || !std::isfinite(opt->max_depth))
         return fail(PDSC_ERR_ARG, "min_depth %g / max_depth %g (need 0 <= min < max, finite)", opt->min_depth,
                     opt->max_depth);
+    if (frames_only) return PDSC_OK;
     for (int l = 0; l < ODO_LEVELS; ++l)
         if (opt->iterations[l] < 0 || opt->iterations[l] > 1000)
             return fail(PDSC_ERR_ARG, "iterations[%d]=%d (need 0 .. 1000)", l, opt->iterations[l]);
@@ -495,6 +500,18 @@ static int odo_check(const void *intensity, const void *depth, int F, int H, int
             return fail(PDSC_ERR_ARG, "pair %d = (%d, %d): need two different frames in [0, %d)", p, pair_src[p],
                         pair_tgt[p], F);
     return PDSC_OK;
+}
+
+// step 1: every frame's three levels, 6 images each
+static void odo_frames(const float *intensity, const float *depth, int F, int H, int W,
+                       const pdsc_rgbd_odometry_options *opt, OdoBufs &B, hipStream_t s) {
+    hipLaunchKernelGGL(odo_prep0_kernel, dim3((unsigned)odo_chunks(H, W, 0), F), dim3(256), 0, s, intensity, depth, H, W,
+                       (float)opt->min_depth, (float)opt->max_depth, B.lv[0].I, B.lv[0].D);
+    for (int l = 1; l < ODO_LEVELS; ++l)
+        hipLaunchKernelGGL(odo_down_kernel, dim3((unsigned)odo_chunks(H, W, l), F), dim3(256), 0, s, B.lv[l - 1].I,
+                           B.lv[l - 1].D, B.lv[l - 1].H, B.lv[l - 1].W, B.lv[l].I, B.lv[l].D);
+    for (int l = 0; l < ODO_LEVELS; ++l)
+        hipLaunchKernelGGL(odo_sobel_kernel, dim3((unsigned)odo_chunks(H, W, l), F), dim3(256), 0, s, B.lv[l]);
 }
 
 // the frames' pyramids, the pair list and the pairs' states; then a_s, a_t (step 2)
@@ -510,13 +527,7 @@ static int odo_setup(const float *intensity, const float *depth, int F, int H, i
     }
     HIPCHK(hipMemcpyAsync(B.pair_src, pair_src, sizeof(int) * P, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(B.pair_tgt, pair_tgt, sizeof(int) * P, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(odo_prep0_kernel, dim3((unsigned)odo_chunks(H, W, 0), F), dim3(256), 0, s, intensity, depth, H, W,
-                       (float)opt->min_depth, (float)opt->max_depth, B.lv[0].I, B.lv[0].D);
-    for (int l = 1; l < ODO_LEVELS; ++l)
-        hipLaunchKernelGGL(odo_down_kernel, dim3((unsigned)odo_chunks(H, W, l), F), dim3(256), 0, s, B.lv[l - 1].I,
-                           B.lv[l - 1].D, B.lv[l - 1].H, B.lv[l - 1].W, B.lv[l].I, B.lv[l].D);
-    for (int l = 0; l < ODO_LEVELS; ++l)
-        hipLaunchKernelGGL(odo_sobel_kernel, dim3((unsigned)odo_chunks(H, W, l), F), dim3(256), 0, s, B.lv[l]);
+    odo_frames(intensity, depth, F, H, W, opt, B, s);
     hipLaunchKernelGGL(odo_init_kernel, dim3((P + 63) / 64), dim3(64), 0, s, B.st, init, P);
     const size_t nk = (size_t)P * H * W;
     hipLaunchKernelGGL(odo_fill_keys_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, B.keys, nk);
@@ -602,6 +613,31 @@ int32_t pdsc_rgbd_odometry_linearize(const float *intensity, const float *depth,
     hipLaunchKernelGGL(odo_lin_kernel, dim3(nc, P), dim3(ODO_CHUNK), 0, s, B.lv[level], B.pair_src, B.pair_tgt, B.st,
                        options->max_depth_diff, 0, B.keys, ks, nc, B.part, ps, corr);
     hipLaunchKernelGGL(odo_sums_out_kernel, dim3(P), dim3(64), 0, s, B.part, ps, nc, sums);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return PDSC_OK;
+}
+
+int32_t pdsc_rgbd_odometry_pyramid(const float *intensity, const float *depth, int32_t F, int32_t H, int32_t W,
+                                   double min_depth, double max_depth, int32_t level, float *I, float *D, float *Idx,
+                                   float *Idy, float *Ddx, float *Ddy, void *ws, size_t ws_bytes, pdsc_stream_t stream) {
+    pdsc_rgbd_odometry_options opt = {};
+    opt.min_depth = min_depth;
+    opt.max_depth = max_depth;
+    RET_IF(odo_check(intensity, depth, F, H, W, 0.0, 0.0, 0.0, 0.0, nullptr, nullptr, 1, &opt, ws, true));
+    if (level < 0 || level >= ODO_LEVELS) return fail(PDSC_ERR_ARG, "level=%d (need 0 .. %d)", level, ODO_LEVELS - 1);
+    RET_IF(need_ws(ws_bytes, pdsc_rgbd_odometry_workspace_bytes(F, H, W, 1)));
+    hipStream_t s = S_(stream);
+    Carve c(ws);
+    OdoBufs B;
+    bind_odo(c, F, H, W, 1, B);
+    odo_frames(intensity, depth, F, H, W, &opt, B, s);
+    const OdoLevel &L = B.lv[level];
+    const size_t bytes = sizeof(float) * (size_t)F * L.H * L.W;
+    float *const out[6] = {I, D, Idx, Idy, Ddx, Ddy};
+    const float *const img[6] = {L.I, L.D, L.Idx, L.Idy, L.Ddx, L.Ddy};
+    for (int k = 0; k < 6; ++k)
+        if (out[k]) HIPCHK(hipMemcpyAsync(out[k], img[k], bytes, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     return PDSC_OK;

@@ -126,6 +126,22 @@ def rgbd_odometry_linearize(intensity, depth, intrinsic, pairs, trans=None, leve
     return corr, JtJ, sums[:, 21:27], sums[:, 27].round().long(), scales
 
 
+def rgbd_odometry_pyramid(intensity, depth, level: int = 0, min_depth: float = 0.0, max_depth: float = 4.0):
+    """Pyramid `level` of all F frames as rgbd_odometry builds it (pdsc_rgbd_odometry_pyramid:
+    step 1 alone): a dict of the six fp32 [F, H_l, W_l] images I, D, Idx, Idy, Ddx, Ddy."""
+    intensity, depth = _dev(intensity, "intensity"), _dev(depth, "depth")
+    if intensity.dim() != 3 or tuple(intensity.shape) != tuple(depth.shape):
+        raise ValueError(f"intensity {tuple(intensity.shape)} and depth {tuple(depth.shape)} must both be [F,H,W]")
+    dev = intensity.device
+    F, H, W = intensity.shape
+    level = int(level)
+    shape = (F, H >> level, W >> level) if 0 <= level < 3 else (F, 1, 1)  # a bad level is the entry's error
+    out = {k: torch.empty(shape, dtype=torch.float32, device=dev) for k in ("I", "D", "Idx", "Idy", "Ddx", "Ddy")}
+    call("pdsc_rgbd_odometry_pyramid", intensity, depth, F, H, W, float(min_depth), float(max_depth), level,
+         *out.values(), device=dev, ws=("pdsc_rgbd_odometry_workspace_bytes", F, H, W, 1))
+    return out
+
+
 class TSDFVolume:
     """o3d.integration.ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) on the
     device (include/pdsc.h f14): at most `max_blocks` blocks of 16^3 voxels, 80 KB

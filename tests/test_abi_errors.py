@@ -187,6 +187,14 @@ ENTRIES = {
          {15: short("pdsc_gc_ransac_workspace_bytes", 100)}],
         [{2: 2, 6: 0}, {6: 0, 3: 0.0}, {4: 1.5, 7: 0.0}, {7: 1.5, 5: 1025}, {5: 0, 0: None},
          {1: None, 15: short("pdsc_gc_ransac_workspace_bytes", 100)}]),
+    # f13 (rgbd_odometry.hip): the pyramid entry, odo_check's frame checks in their order
+    "pdsc_rgbd_odometry_pyramid": (
+        [P, P, 2, 8, 16, 0.0, 4.0, 0, P, None, None, None, None, None, P, BIG, None],
+        [{0: None}, {1: None}, {14: None}, {2: 0}, {3: 4}, {4: 4}, {3: 10}, {4: 18}, {2: 65536}, {3: 8192, 4: 8196},
+         {5: -1.0}, {5: "nan"}, {6: 0.0}, {5: 4.0}, {6: "inf"}, {7: -1}, {7: 3},
+         {15: short("pdsc_rgbd_odometry_workspace_bytes", 2, 8, 16, 1)}],
+        [{0: None, 2: 0}, {2: 0, 3: 4}, {3: 4, 2: 65536}, {2: 65536, 6: 0.0}, {6: 0.0, 7: 3},
+         {7: 3, 15: short("pdsc_rgbd_odometry_workspace_bytes", 2, 8, 16, 1)}]),
     # a1 (compat.hip)
     "pdsc_compat_f32": (
         [P, P, 2, 10, P, P, None],

@@ -57,6 +57,35 @@ def test_odometry_errors(lin):
     assert odo(lib, H=8192, W=8196, linearize=lin, ws_bytes=1 << 50) == ERR_UNSUPPORTED and b"2^26" in lib.pdsc_last_error()
 
 
+def pyr(lib, F=2, H=48, W=64, mn=0.0, mx=4.0, level=0, intensity=P, depth=P, outs=(P, P, P, P, P, P), ws=P,
+        ws_bytes=None):
+    nb = lib.pdsc_rgbd_odometry_workspace_bytes(F, H, W, 1) if ws_bytes is None else ws_bytes
+    return lib.pdsc_rgbd_odometry_pyramid(intensity, depth, F, H, W, mn, mx, level, *outs, ws, nb, None)
+
+
+def test_pyramid_errors():
+    """The frame checks of pdsc_rgbd_odometry, message for message (one predicate), and no pair checks."""
+    lib = _lib.load()
+    for name in ("intensity", "depth", "ws"):
+        assert pyr(lib, **{name: None}) == ERR_ARG and b"null" in lib.pdsc_last_error(), name
+    assert pyr(lib, F=0, ws_bytes=1 << 40) == ERR_ARG and b"F=0 P=1" in lib.pdsc_last_error()
+    for H, W in ((4, 64), (48, 4), (50, 64), (48, 66), (7, 7)):
+        assert pyr(lib, H=H, W=W, ws_bytes=1 << 40) == ERR_ARG
+        msg = lib.pdsc_last_error()
+        assert odo(lib, H=H, W=W, ws_bytes=1 << 40) == ERR_ARG and lib.pdsc_last_error() == msg
+    for mn, mx in ((2.0, 1.0), (-1.0, 4.0), (math.nan, 4.0), (0.0, math.inf), (1.0, 1.0)):
+        assert pyr(lib, mn=mn, mx=mx) == ERR_ARG
+        msg = lib.pdsc_last_error()
+        assert odo(lib, mn=mn, mx=mx) == ERR_ARG and lib.pdsc_last_error() == msg and b"min_depth" in msg
+    for level in (-1, 3):
+        assert pyr(lib, level=level) == ERR_ARG and b"level" in lib.pdsc_last_error()
+    nb = lib.pdsc_rgbd_odometry_workspace_bytes(2, 48, 64, 1)
+    assert pyr(lib, ws_bytes=nb - 1) == ERR_ARG and b"workspace too small" in lib.pdsc_last_error()
+    assert pyr(lib, F=70000, ws_bytes=1 << 40) == ERR_UNSUPPORTED
+    assert pyr(lib, H=8192, W=8196, ws_bytes=1 << 50) == ERR_UNSUPPORTED and b"2^26" in lib.pdsc_last_error()
+    assert pyr(lib, F=1, level=3) == ERR_ARG and b"level" in lib.pdsc_last_error()  # one frame is enough: no pair is needed
+
+
 def test_odometry_workspace_is_monotone():
     q = _lib.load().pdsc_rgbd_odometry_workspace_bytes
     assert q(0, 48, 64, 1) == 0 and q(2, 48, 64, 0) == 0 and q(2, 6, 64, 1) == 0 and q(2, 48, 62, 1) == 0
